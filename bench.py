@@ -31,8 +31,17 @@ thread on every CPU the process may use (the affinity mask capped by the cgroup 
 quota: 16 of the 256 visible CPUs on the GPU box), with the per-core rate and its
 linear extrapolation to every visible CPU.
 
-Launch: python bench.py [--gpus N --steps K --warmup W]; N > 1 under
-torch.distributed.run (one process per GPU, RCCL).
+A plain run (python bench.py [--gpus N --steps K --warmup W]) sets up, warms up, times
+the K steps above and prints the result line: metric, value, unit, ms_per_step, the
+roofline and breakdown of the timed steps.  Everything else described here -- the
+config_C block with its shard and frustrated sub-blocks, asteps_DE, mstep_DE and the CPU
+baselines -- takes runs of its own and is measured only with --full (the keys are null in
+a plain run's line).  --dump-outputs DIR writes what the last timed step computed
+(dump_outputs below) as DIR/<name>.npy; the inputs are seeded, so two builds run with the
+same arguments can be compared output for output.
+
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR];
+N > 1 under torch.distributed.run (one process per GPU, RCCL).
 """
 import argparse
 import json
@@ -46,6 +55,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E (MI355X_MICROARCH.md)
+DUMP_SMALL_BYTES = 6 * 1000 * 1000   # --dump-outputs: at most this much of each of rows / info / records,
+DUMP_COORD_BYTES = 40 * 1000 * 1000  # and of the coordinates: under 64 MB in all
 
 
 def parse():
@@ -53,6 +64,13 @@ def parse():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=2)
     ap.add_argument('--warmup', type=int, default=1)
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what takes runs of its own: the CPU baselines, the D/E A-steps, the '
+                         'config C block with its shard sub-blocks and the D/E M-steps (each still subject to '
+                         'its own switch below); a plain run times only the --steps A/M iterations')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last one computed (coordinates, A-step rows, '
+                         'per-structure optimisation info, violation records) as DIR/<name>.npy')
     ap.add_argument('--config', choices=['B', 'C'], default='B',
                     help='B: 2 Mb diploid (the N=1 metric workload); C: 200 kb diploid (29 838 beads)')
     ap.add_argument('--nstruct', type=int, default=None, help='structures per GPU (B: 1000, C: 125)')
@@ -266,6 +284,51 @@ def cpu_baseline_astep(args, it, nthreads, npairs=4000):
     return {'value': len(sub) / dt, 'unit': 'pairs/s', 'cores': nthreads, 'kind': 'port',
             'per_core': len(sub) / dt / nthreads,
             'sample': '%d seeded pairs of the same list, %d structures, %.2f s' % (len(sub), it.S_total, dt)}
+
+
+def sample_rows(a, max_bytes, seed=0):
+    """`a` when it fits max_bytes, else a fixed seeded sample of its rows (leading axis, kept
+    in order) with their indices: (array, indices or None).  The sample depends on the
+    shape and the seed alone, so two runs with the same arguments pick the same rows."""
+    n = len(a)
+    if a.nbytes <= max_bytes or n <= 1:
+        return a, None
+    per = a.nbytes // n + 8  # a row and its index
+    k = max(1, min(n, int(max_bytes // per)))
+    idx = np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+    return a[idx], idx
+
+
+def dump_outputs(it, path, rank=0, world=1):
+    """What the last timed A/M iteration computed, as `path`/<name>.npy (float32 / float64;
+    <name>_rank<r>.npy for this rank's share when N > 1), under 64 MB in all:
+      coordinates      (S, natom, 3) f32  the structures after the M-step
+      actdist_rows     (rows, 4)     f64  the A-step's rows: row, col, dist, prob
+      optinfo          (S, 14)       f64  igm_opt_info per structure, fields in declaration order
+      violation_stats  (S, classes, 104) f64  the violation records of the M-step
+    An array over its share is cut to a seeded sample of its rows (sample_rows), whose
+    indices go to <name>_index.npy.  Returns the files written."""
+    from igm_amd._lib import optinfo_dtype, row_dtype
+    os.makedirs(path, exist_ok=True)
+    rows = it.rows[:it.nrows * row_dtype.itemsize].cpu().numpy().view(row_dtype)
+    info = it.info.cpu().numpy().view(optinfo_dtype)
+    arrays = [
+        ('coordinates', it.xyz.cpu().numpy().astype(np.float32, copy=False), DUMP_COORD_BYTES),
+        ('actdist_rows', np.stack([rows[k].astype(np.float64) for k in ('row', 'col', 'dist', 'prob')], 1),
+         DUMP_SMALL_BYTES),
+        ('optinfo', np.concatenate([info[k].reshape(len(info), -1).astype(np.float64)
+                                    for k in optinfo_dtype.names], 1), DUMP_SMALL_BYTES),
+        ('violation_stats', it.stats.cpu().numpy().astype(np.float64), DUMP_SMALL_BYTES),
+    ]
+    sfx = '' if world == 1 else '_rank%d' % rank
+    written = []
+    for name, a, cap in arrays:
+        a, idx = sample_rows(np.ascontiguousarray(a), cap)
+        for nm, v in ((name, a),) + (((name + '_index', idx.astype(np.float64)),) if idx is not None else ()):
+            p = os.path.join(path, nm + sfx + '.npy')
+            np.save(p, v)
+            written.append(p)
+    return written
 
 
 def max_over_ranks(dt, world, dev):
@@ -736,7 +799,7 @@ def main():
         progress('config %s warmup %d/%d' % (args.config, w + 1, args.warmup))
         it.step()
     barrier()
-    want_cpu = args.cpu_sample != 0 and world == 1 and rank == 0
+    want_cpu = args.full and args.cpu_sample != 0 and world == 1 and rank == 0
     snap = it.snapshot() if want_cpu else None  # the first timed step's input state
     anneal_ms, bytes_launch, astep_s, mstep_s = [], [], [], []
     t0 = time.perf_counter()
@@ -756,25 +819,29 @@ def main():
     score = it.violation_score()
     info = it.info_host()
     nrows, nbonds, S_local, npairs, npairs_total = int(it.nrows), it.nbonds, it.S_local, it.npairs, it.npairs_total
+    if args.dump_outputs:  # before the baselines below rewind the loop state to the snapshot
+        progress('writing outputs')
+        dump_outputs(it, args.dump_outputs, rank, world)
     de = cblock = astep_cpu = cpu = mde = None
     if want_cpu:
         progress('CPU baselines of config %s' % args.config)
         nth, _, _ = host_threads(args)
         astep_cpu = cpu_baseline_astep(args, it, nth, npairs=2000 * nth)
         cpu = cpu_baseline(args, it, inp, snap)
-    if rank == 0 and world == 1 and not args.no_de:  # the N=1 line carries it; scaling runs stay lean
+    if args.full and rank == 0 and world == 1 and not args.no_de:  # the N=1 line carries it; scaling runs stay lean
         progress('configuration D/E A-steps')
         de = bench_asteps_de(args, it.ctx)
     del it, snap
     torch.cuda.empty_cache()
-    if args.config == 'B' and not args.no_c:  # every rank: the 200 kb pop=c_total population, strong split
+    # every rank: the 200 kb pop=c_total population, strong split
+    if args.full and args.config == 'B' and not args.no_c:
         cblock = bench_config_c(args, dev, world, rank, local, backend)
         if world == 1 and args.c_shard > 0 and args.c_shard != args.c_total:
             cblock['shard%d' % args.c_shard] = bench_shard(args, dev)
             if not args.no_mstep_de:
                 cblock['shard%d_frustrated' % args.c_shard] = bench_frustrated(args, dev, args.c_shard)
                 torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and args.config == 'B' and not args.no_mstep_de:
+    if args.full and rank == 0 and world == 1 and args.config == 'B' and not args.no_mstep_de:
         n = args.c_shard if args.c_shard > 0 else 125
         mde = {}
         for cfg in ('D', 'E'):

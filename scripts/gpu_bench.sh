@@ -15,10 +15,10 @@ HB=$!
 trap 'kill $HB 2>/dev/null' EXIT
 BARGS=${BARGS:-}
 if [ -z "$NOBENCH" ]; then
-  timeout -k 10 900 python -u bench.py $BARGS > $OUT/bench.log 2>&1
+  timeout -k 10 900 python -u bench.py --full $BARGS > $OUT/bench.log 2>&1
   rc=$?; echo "bench rc=$rc"; grep "^{" $OUT/bench.log | cut -c1-300; [ $rc -eq 0 ] || exit $rc
 fi
-PARGS=${PARGS:-"--steps 2 --warmup 1 --cpu-sample 0 --no-de --no-c $BARGS"}
+PARGS=${PARGS:-"--full --steps 2 --warmup 1 --cpu-sample 0 --no-de --no-c $BARGS"}
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt -- python3 bench.py $PARGS > $OUT/prof_kt.log 2>&1
 rc=$?; echo "kt rc=$rc"; [ $rc -eq 0 ] || exit $rc
 timeout -k 10 600 rocprofv3 --pmc FETCH_SIZE -d $OUT/fetch -o fetch -- python3 bench.py $PARGS > $OUT/prof_fetch.log 2>&1

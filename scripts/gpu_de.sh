@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 timeout -k 10 600 python -u -m pytest -x -q --timeout 300 --timeout-method thread tests/test_asteps_gpu.py \
   tests/test_polymer.py tests/test_steps_de.py -m gpu > $OUT/pytest.log 2>&1
 rc=$?; tail -2 $OUT/pytest.log; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 python bench.py --steps 1 --warmup 0 --protocol-scale 0.02 --cpu-sample 0 --no-c > $OUT/b.jsonl \
+timeout -k 10 300 python bench.py --full --steps 1 --warmup 0 --protocol-scale 0.02 --cpu-sample 0 --no-c > $OUT/b.jsonl \
   2>/dev/null || exit $?
 python - $OUT/b.jsonl <<'PY'
 import json, sys
@@ -17,7 +17,7 @@ for k in ('damid', 'fish', 'sprite', 'polymer'):
     print('%-8s %8.3f ms %6.0f GB/s' % (k, d[k]['ms'], d[k]['achieved_GBps']))
 PY
 [ -n "$NOKT" ] && exit 0
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt -- python3 bench.py --steps 1 --warmup 0 \
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt -- python3 bench.py --full --steps 1 --warmup 0 \
   --protocol-scale 0.01 --cpu-sample 0 --no-c > $OUT/kt.log 2>&1 || exit $?
 python3 - $OUT/kt > $OUT/kernels_de.txt <<'PY'
 import glob, sqlite3, sys

@@ -9,7 +9,7 @@ n=0
 IFS=';' read -ra SS <<< "${SETS:-SQ_WAVES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE}"
 for cs in "${SS[@]}"; do
   n=$((n+1))
-  timeout -s KILL 300 rocprofv3 --pmc $cs -d $OUT/p$n -o p -- python3 bench.py ${ARGS:---steps 1 --warmup 0 \
+  timeout -s KILL 300 rocprofv3 --pmc $cs -d $OUT/p$n -o p -- python3 bench.py ${ARGS:---full --steps 1 --warmup 0 \
     --protocol-scale 0.02 --cpu-sample 0 --no-c} > $OUT/p$n.log 2>&1
   rc=$?; [ $rc -eq 0 ] || { echo "pass $n rc=$rc"; tail -3 $OUT/p$n.log; exit $rc; }
   python3 - $OUT/p$n "${MATCH:-%}" <<'PY'
