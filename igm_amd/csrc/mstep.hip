@@ -280,6 +280,28 @@ __device__ __forceinline__ void block_scan(const InT* in, OutT* out, int n, int*
 }
 
 // --------------------------------------------------------- neighbour build
+// A cell grid may hold at most cap cells.  The builds size the cell side cs from a box
+// volume that counts an axis thinner than cut_list as cut_list wide; such an axis keeps
+// its one cell however large cs grows, so the product of the floors can still pass the cap
+// (a planar structure with a far outlier: 1273 x 5 x 1 cells against a cap of 4096 -- past
+// the cell arrays).  The axis with the most cells then gives up the excess: its cells grow
+// wider than cs, and any side >= cut_list is a valid grid.  Integer only, and a grid within
+// the cap is untouched.  (Found by reading; pinned by the 'plane_outlier' case of tests/test_mstep_sizes_gpu.py.)
+__device__ __forceinline__ int3 grid_cap(int a, int b, int c, int cap) {
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+        if ((long)a * b * c > (long)cap) {
+            const bool ma = a >= b && a >= c, mb = !ma && b >= c;
+            const long o = ma ? (long)b * c : (mb ? (long)a * c : (long)a * b);  // cells of the other two axes
+            const int q = o < (long)cap ? cap / (int)o : 1;
+            a = ma ? q : a;
+            b = mb ? q : b;
+            c = (ma || mb) ? c : q;
+        }
+    }
+    return make_int3(a, b, c);
+}
+
 template <typename T>
 __device__ __forceinline__ int cell_index(T x, T y, T z, const T* lo, const T* inv, const int* nb) {
     const T pp[3] = {x, y, z};
@@ -376,9 +398,18 @@ __device__ __noinline__ unsigned long long build_nlist(int natom, const vec4_t<T
         if (vol / (cs * cs * cs) > (float)L.cellcap) cs = cbrtf(vol / (float)L.cellcap) * 1.0001f;
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
-            lo[d] = (T)(-mm[d]);
             nb[d] = (int)floorf(ext[d] / cs);
             if (nb[d] < 1) nb[d] = 1;
+        }
+        {
+            const int3 g = grid_cap(nb[0], nb[1], nb[2], L.cellcap);
+            nb[0] = g.x;
+            nb[1] = g.y;
+            nb[2] = g.z;
+        }
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            lo[d] = (T)(-mm[d]);
             inv[d] = ext[d] > 0.0f ? (T)((float)nb[d] / ext[d]) : T(0);
         }
     }
@@ -525,9 +556,18 @@ __device__ __noinline__ unsigned long long build_nlist_lds(int natom, int nwalk,
         if (vol / (cs * cs * cs) > (float)Lg.cellcap) cs = cbrtf(vol / (float)Lg.cellcap) * 1.0001f;
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
-            lo[d] = -mm[d];
             nb[d] = (int)floorf(ext[d] / cs);
             if (nb[d] < 1) nb[d] = 1;
+        }
+        {
+            const int3 g = grid_cap(nb[0], nb[1], nb[2], Lg.cellcap);
+            nb[0] = g.x;
+            nb[1] = g.y;
+            nb[2] = g.z;
+        }
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            lo[d] = -mm[d];
             inv[d] = ext[d] > 0.0f ? (float)nb[d] / ext[d] : 0.0f;
         }
     }
@@ -1710,6 +1750,12 @@ __device__ __forceinline__ void pop_grid_of(const PopArgs& A, int s, const float
     for (int d = 0; d < 3; ++d) {
         nbv[d] = (int)floorf(d == 0 ? ext[d] * qx / cs : ext[d] / cs);
         if (nbv[d] < 1) nbv[d] = 1;
+    }
+    {
+        const int3 g = grid_cap(nbv[0], nbv[1], nbv[2], A.ccap);
+        nbv[0] = g.x;
+        nbv[1] = g.y;
+        nbv[2] = g.z;
     }
     // x cells a pair within cut_list can be apart (the cell walk's x reach)
     if (store) gn[3] = ext[0] > 0.0f ? max(1, (int)ceilf(cut * (float)nbv[0] / ext[0] * 1.00001f)) : 1;

@@ -68,10 +68,11 @@ def _mlib():
         L.oracle_mstep_run.argtypes = [vp, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, i32]
         L.oracle_mstep_run_sf.restype = ctypes.c_int
         L.oracle_mstep_run_sf.argtypes = [vp, i32, i32, vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, i32]
-        L.oracle_mstep_forces.restype = ctypes.c_int
-        L.oracle_mstep_forces.argtypes = [vp, i32, i32, vp, vp, vp, vp, i64, vp, vp, f64, f64, vp, vp]
-        L.oracle_mstep_md.restype = ctypes.c_int
-        L.oracle_mstep_md.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, i64, vp, vp, f64, f64, f64, f64, f64, i32, i32]
+        L.oracle_mstep_forces_sf.restype = ctypes.c_int
+        L.oracle_mstep_forces_sf.argtypes = [vp, i32, i32, vp, vp, vp, i64, vp, i64, vp, vp, f64, f64, vp, vp, i32]
+        L.oracle_mstep_md_sf.restype = ctypes.c_int
+        L.oracle_mstep_md_sf.argtypes = [vp, i32, i32, vp, vp, vp, vp, i64, vp, i64, vp, vp, f64, f64, f64, f64, f64,
+                                         i32, i32]
         L.oracle_velocity_create.restype = ctypes.c_int
         L.oracle_velocity_create.argtypes = [i32, vp, f64, i32, vp]
         L.oracle_hic_select.restype = ctypes.c_int
@@ -133,7 +134,8 @@ def set_volume(vol):
     L.oracle_set_volume(int(vol['body_idx']), n.ctypes.data, o.ctypes.data, g.ctypes.data, m.ctypes.data)
 
 
-def mstep_forces(params, xyz, radii, flags, shared, sptr, sbonds, evf, envf):
+def mstep_forces(params, xyz, radii, flags, shared, sptr, sbonds, evf, envf, nthreads=1):
+    """flags (N,) shared or (S, N) one row per structure."""
     import ctypes as C
     xyz = np.ascontiguousarray(xyz, np.float32)
     S, N = xyz.shape[0], xyz.shape[1]
@@ -142,9 +144,11 @@ def mstep_forces(params, xyz, radii, flags, shared, sptr, sbonds, evf, envf):
     e = np.zeros((S, 7), np.float64)
     radii = _c(radii, np.float32)
     flags = _c(flags, np.uint32)
-    _mlib().oracle_mstep_forces(C.byref(params), S, N, xyz.ctypes.data, radii.ctypes.data, flags.ctypes.data,
-                                shared.ctypes.data, len(shared), sptr.ctypes.data, sbonds.ctypes.data,
-                                float(evf), float(envf), f.ctypes.data, e.ctypes.data)
+    assert flags.shape[-1] == N and (flags.ndim == 1 or flags.shape[0] == S)
+    _mlib().oracle_mstep_forces_sf(C.byref(params), S, N, xyz.ctypes.data, radii.ctypes.data, flags.ctypes.data,
+                                   N if flags.ndim == 2 else 0, shared.ctypes.data, len(shared), sptr.ctypes.data,
+                                   sbonds.ctypes.data, float(evf), float(envf), f.ctypes.data, e.ctypes.data,
+                                   int(nthreads))
     return f, e
 
 
@@ -156,10 +160,11 @@ def mstep_md(params, x, v, radii, flags, shared, sptr, sbonds, evf, envf, t0, t1
     shared, sptr, sbonds = _bonds(shared, sptr, sbonds, S)
     radii = _c(radii, np.float32)
     flags = _c(flags, np.uint32)
-    _mlib().oracle_mstep_md(C.byref(params), S, N, x.ctypes.data, v.ctypes.data, radii.ctypes.data,
-                            flags.ctypes.data, shared.ctypes.data, len(shared), sptr.ctypes.data,
-                            sbonds.ctypes.data, float(evf), float(envf), float(t0), float(t1), float(xmax),
-                            int(nsteps), int(nthreads))
+    assert flags.shape[-1] == N and (flags.ndim == 1 or flags.shape[0] == S)
+    _mlib().oracle_mstep_md_sf(C.byref(params), S, N, x.ctypes.data, v.ctypes.data, radii.ctypes.data,
+                               flags.ctypes.data, N if flags.ndim == 2 else 0, shared.ctypes.data, len(shared),
+                               sptr.ctypes.data, sbonds.ctypes.data, float(evf), float(envf), float(t0), float(t1),
+                               float(xmax), int(nsteps), int(nthreads))
     return x, v
 
 

@@ -140,9 +140,15 @@ static void build_neighbors(model_t* m) {
     for (int d = 0; d < 3; ++d) vol *= (hi[d] - lo[d] > cut ? hi[d] - lo[d] : cut);
     double cs = cut;
     if (vol / (cs * cs * cs) > m->nbins_cap) cs = cbrt(vol / m->nbins_cap);
-    for (int d = 0; d < 3; ++d) {
-        nbin[d] = (int)floor((hi[d] - lo[d]) / cs);
-        if (nbin[d] < 1) nbin[d] = 1;
+    for (;;) {
+        for (int d = 0; d < 3; ++d) {
+            nbin[d] = (int)floor((hi[d] - lo[d]) / cs);
+            if (nbin[d] < 1) nbin[d] = 1;
+        }
+        /* vol counts an axis thinner than cut as cut wide, but that axis keeps its one bin
+         * however large cs grows: a planar structure with a far outlier can still pass the cap */
+        if ((long long)nbin[0] * nbin[1] * nbin[2] <= (long long)m->nbins_cap) break;
+        cs *= 1.05;
     }
     const int ntot = nbin[0] * nbin[1] * nbin[2];
     for (int b = 0; b < ntot; ++b) m->bin_head[b] = -1;
@@ -730,15 +736,17 @@ int oracle_mstep_run(const igm_mstep_params* p, int32_t nstruct, int32_t natom, 
                                nthreads);
 }
 
-/* forces (f64) and energies {total, pair, bond, env0..3} */
-int oracle_mstep_forces(const igm_mstep_params* p, int32_t nstruct, int32_t natom, const float* xyz,
-                        const float* radii, const uint32_t* fl, const igm_bond* shared, int64_t nshared,
-                        const int64_t* sptr, const igm_bond* sbonds, double evf, double envf, double* forces,
-                        double* energies) {
+/* forces (f64) and energies {total, pair, bond, env0..3}; fl_stride as in oracle_mstep_run_sf */
+int oracle_mstep_forces_sf(const igm_mstep_params* p, int32_t nstruct, int32_t natom, const float* xyz,
+                           const float* radii, const uint32_t* fl, int64_t fl_stride, const igm_bond* shared,
+                           int64_t nshared, const int64_t* sptr, const igm_bond* sbonds, double evf, double envf,
+                           double* forces, double* energies, int32_t nthreads) {
+#pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads > 0 ? nthreads : 1)
     for (int s = 0; s < nstruct; ++s) {
         model_t m;
         const int64_t b0 = sptr ? sptr[s] : 0, b1 = sptr ? sptr[s + 1] : 0;
-        model_init(&m, p, natom, xyz + (size_t)s * natom * 3, radii, fl, shared, nshared, sbonds + b0, b1 - b0);
+        model_init(&m, p, natom, xyz + (size_t)s * natom * 3, radii, fl + (size_t)s * fl_stride, shared, nshared,
+                   sbonds + b0, b1 - b0);
         m.evf = evf;
         m.envf = envf;
         const double e = energy_force(&m);
@@ -753,18 +761,26 @@ int oracle_mstep_forces(const igm_mstep_params* p, int32_t nstruct, int32_t nato
     return 0;
 }
 
-/* short MD segment from given x, v (f64 in/out) */
-int oracle_mstep_md(const igm_mstep_params* p, int32_t nstruct, int32_t natom, double* x, double* v,
-                    const float* radii, const uint32_t* fl, const igm_bond* shared, int64_t nshared,
-                    const int64_t* sptr, const igm_bond* sbonds, double evf, double envf, double t0, double t1,
-                    double xmax, int32_t nsteps, int32_t nthreads) {
+int oracle_mstep_forces(const igm_mstep_params* p, int32_t nstruct, int32_t natom, const float* xyz,
+                        const float* radii, const uint32_t* fl, const igm_bond* shared, int64_t nshared,
+                        const int64_t* sptr, const igm_bond* sbonds, double evf, double envf, double* forces,
+                        double* energies) {
+    return oracle_mstep_forces_sf(p, nstruct, natom, xyz, radii, fl, 0, shared, nshared, sptr, sbonds, evf, envf,
+                                  forces, energies, 1);
+}
+
+/* short MD segment from given x, v (f64 in/out); fl_stride as in oracle_mstep_run_sf */
+int oracle_mstep_md_sf(const igm_mstep_params* p, int32_t nstruct, int32_t natom, double* x, double* v,
+                       const float* radii, const uint32_t* fl, int64_t fl_stride, const igm_bond* shared,
+                       int64_t nshared, const int64_t* sptr, const igm_bond* sbonds, double evf, double envf,
+                       double t0, double t1, double xmax, int32_t nsteps, int32_t nthreads) {
 #pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads > 0 ? nthreads : 1)
     for (int s = 0; s < nstruct; ++s) {
         float* xf = (float*)malloc(sizeof(float) * 3 * natom);
         model_t m;
         const int64_t b0 = sptr ? sptr[s] : 0, b1 = sptr ? sptr[s + 1] : 0;
         for (int i = 0; i < 3 * natom; ++i) xf[i] = (float)x[(size_t)s * natom * 3 + i];
-        model_init(&m, p, natom, xf, radii, fl, shared, nshared, sbonds + b0, b1 - b0);
+        model_init(&m, p, natom, xf, radii, fl + (size_t)s * fl_stride, shared, nshared, sbonds + b0, b1 - b0);
         memcpy(m.x, x + (size_t)s * natom * 3, sizeof(double) * 3 * natom);
         build_neighbors(&m);
         memcpy(m.v, v + (size_t)s * natom * 3, sizeof(double) * 3 * natom);
@@ -777,6 +793,14 @@ int oracle_mstep_md(const igm_mstep_params* p, int32_t nstruct, int32_t natom, d
         free(xf);
     }
     return 0;
+}
+
+int oracle_mstep_md(const igm_mstep_params* p, int32_t nstruct, int32_t natom, double* x, double* v,
+                    const float* radii, const uint32_t* fl, const igm_bond* shared, int64_t nshared,
+                    const int64_t* sptr, const igm_bond* sbonds, double evf, double envf, double t0, double t1,
+                    double xmax, int32_t nsteps, int32_t nthreads) {
+    return oracle_mstep_md_sf(p, nstruct, natom, x, v, radii, fl, 0, shared, nshared, sptr, sbonds, evf, envf, t0, t1,
+                              xmax, nsteps, nthreads);
 }
 
 /* velocity create only (for RNG-stream parity tests) */
