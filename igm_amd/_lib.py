@@ -133,6 +133,8 @@ SIGNATURES = {
                               _i32, _i32, _vp, _vp, _vp, ctypes.POINTER(_i64)]),
     'igm_population_transpose': (_i32, [_vp, _u32, _i32, _i32, _i32, _vp, _vp, _i32]),
     'igm_mstep_set_volumes': (_i32, [_vp, _i32, _vp, _vp, _i32]),
+    'igm_mstep_set_envelope_maps': (_i32, [_vp, _i32, _vp, _i32]),
+    'igm_volume_select': (_i32, [_vp, _u32, _i32, _i32, _vp, _vp, _i64, _vp, _u32, _vp, _i32, _vp, _vp]),
     'igm_mstep_violations': (_i32, [_vp, _u32, ctypes.POINTER(MStepParams), _i32, _i32, _vp, _vp, _vp,
                                     _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _f64, _vp]),
 }

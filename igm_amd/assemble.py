@@ -9,9 +9,16 @@ as the flat arrays the batched engine consumes.
   PolymerDistrib    polymer_bis.py:50-90 (:236-249)     per-structure bonds, class POLYMER
   Envelope          envelope.py:36-62 (:252-262)        envelope 0 (ellipsoid, all beads)
   GenEnvelope       genenvelope.py:37-58 (:263-274)     envelope 0 ('volume': per-structure map)
+  GenEnvelope       nucleolus (:306-323)                next envelope ('volume', k > 0, all beads)
+                                                        on the nucleolus maps of the pool
+  GenDamid          nuclDamID (:331-371)                next envelope ('volume', k < 0) on the
+                                                        nucleolus maps (igm_volume_select)
   interHiC/intraHiC inter_hic.py / intra_hic.py (:376)  per-structure bonds (igm_hic_select)
-  Damid             damid.py:112-143 (:402-440)         envelope 1 (k < 0) on per-structure
+  Damid             damid.py:112-143 (:402-440)         last envelope (k < 0) on per-structure
                                                         atom flags (igm_damid_select)
+  GenDamid          gendamid.py:87-128 (:420-436)       the same on an exp_map nucleus: 'volume',
+                                                        k < 0, the structure's own nucleus map
+                                                        (igm_volume_select)
   Sprite            sprite.py:36-71 (:456-480)          centroid slots + per-structure bonds
   Fish              fish.py:85-266 (:482-503)           per-structure bonds to the centre
 
@@ -62,7 +69,9 @@ def envelope_spec(shape, radius=None, semiaxes=None, k=1.0):
 class DeviceSelect(object):
     """The per-structure selections of the assembly on the GPU (the product path):
     interHiC/intraHiC (igm_hic_select), Damid._apply_envelope membership
-    (igm_damid_select), the staging of the volumetric maps."""
+    (igm_damid_select), the staging of the volumetric maps; for the nuclear-body
+    sections, one envelope's own map table (igm_mstep_set_envelope_maps) and GenDamid's
+    membership (igm_volume_select)."""
 
     def __init__(self, ctx):
         self.ctx = ctx
@@ -80,6 +89,14 @@ class DeviceSelect(object):
         from . import volume as V
         V.stage(self.ctx, vols, struct_map)
 
+    def envelope_maps(self, env_index, pool_index):
+        from . import volume as V
+        V.set_envelope_maps(self.ctx, env_index, pool_index)
+
+    def volume_select(self, x, rows, pool_index, env_index, base):
+        from . import restraints as R
+        return R.volume_envelope_flags(x, rows, pool_index, env_index, base, ctx=self.ctx)[0]
+
 
 def build(xyz, sids, index, spec, ctx, select=None):
     """xyz: (S, nbead, 3) float32 bead coordinates of the batch (struct-major);
@@ -91,7 +108,11 @@ def build(xyz, sids, index, spec, ctx, select=None):
       envelope  envelope_spec(...) or {'shape': 'exp_map', 'k', 'volumes' [maps],
                 'struct_map' (S,) map index per structure, 'files' [names]},
       hic       {rows, contact_range, k} or None,
-      damid     {rows, contact_range, k} or None,
+      damid     {rows, contact_range, k} or None (on an exp_map envelope: GenDamid, with
+                'repr_k' / 'repr_cr' as written in the config for the vstat key),
+      nucleolus {'k', 'shape', 'volumes' [maps], 'struct_map' (S,), 'files' [names]} or None
+                (exp_map envelope only),
+      nucldamid {rows, contact_range, k} or None (needs nucleolus),
       sprite    {assignment, indptr, selected, volume_fraction, k} or None,
       fish      {data (fish_assignment dict), rtype, tol, k} or None.
     ctx: the igm context of the device; select: the selection backend (default
@@ -129,8 +150,15 @@ def build(xyz, sids, index, spec, ctx, select=None):
     env = spec['envelope']
     envelopes, env_scale, env_names = [], [], []
     volumes = None
+    nu, nd = spec.get('nucleolus'), spec.get('nucldamid')
+    if (nu is not None or nd is not None) and env['shape'] != 'exp_map':
+        # the reference itself fails here (ModelingStep.py:326 and :347-370)
+        raise NotImplementedError('nucleolus / nuclDamID need an exp_map nucleus envelope')
+    if nd is not None and nu is None:
+        raise NotImplementedError('nuclDamID needs the maps of model/restraints/nucleolus')
     if env['shape'] == 'exp_map':
-        volumes = env['volumes']
+        # one pool: the nucleus maps, then the nucleolus maps
+        volumes = list(env['volumes']) + (list(nu['volumes']) if nu is not None else [])
         sel.volumes(volumes, env.get('struct_map'))
         envelopes.append(('volume', float(env['k'])))
         env_scale.append(0.95)  # ExpEnvelope contact_range (genenvelope.py:49)
@@ -146,10 +174,39 @@ def build(xyz, sids, index, spec, ctx, select=None):
         env_names.append('Envelope[shape={},k={},a={},b={},c={}]'.format(
             env['shape'], env.get('repr_k', env['k']), *env.get('repr_abc', abc)))
     flags = base
+    nu_pool = None
+    if nu is not None:  # GenEnvelope of the nucleolus maps over every bead (ModelingStep.py:306-323)
+        e = len(envelopes)
+        nu_smap = nu.get('struct_map')
+        nu_pool = len(env['volumes']) + (np.zeros(S, np.int32) if nu_smap is None else np.asarray(nu_smap, np.int32))
+        sel.envelope_maps(e, nu_pool)
+        base[:nbead] |= np.uint32(IGM_ATOM_ENV0 << e)
+        envelopes.append(('volume', float(nu['k'])))
+        env_scale.append(0.95)
+        nfiles = nu.get('files') or ['nucleolus%d' % m for m in range(len(nu['volumes']))]
+        env_names.append(['ExpEnvelope[shape={},map={},k={}]'.format(
+            nu.get('shape', 'exp_map'), nfiles[int(nu_pool[q]) - len(env['volumes'])], nu.get('repr_k', nu['k']))
+            for q in range(S)])
+    if nd is not None:  # GenDamid on the nucleolus maps (ModelingStep.py:351-371, map name as :316)
+        e = len(envelopes)
+        sel.envelope_maps(e, nu_pool)
+        flags = sel.volume_select(x, nd['rows'], nu_pool, e, flags)
+        envelopes.append(('volume', -float(nd['k'])))
+        env_scale.append(float(nd['contact_range']))
+        env_names.append(['LaminaDamID[shape={},map={},k={}, cr={}]'.format(
+            env['shape'], nfiles[int(nu_pool[q]) - len(env['volumes'])], -nd.get('repr_k', nd['k']),
+            nd.get('repr_cr', nd['contact_range'])) for q in range(S)])
     dm = spec.get('damid')
-    if dm is not None:
-        if env['shape'] not in ('sphere', 'ellipsoid'):
-            raise NotImplementedError('DamID with a %s envelope (GenDamid) is not implemented' % env['shape'])
+    if dm is not None and env['shape'] == 'exp_map':  # GenDamid on the structure's own nucleus map
+        e = len(envelopes)
+        own = np.zeros(S, np.int32) if smap is None else np.asarray(smap, np.int32)
+        flags = sel.volume_select(x, dm['rows'], own, e, flags)
+        envelopes.append(('volume', -float(dm['k'])))
+        env_scale.append(float(dm['contact_range']))  # ExpEnvelope's k < 0 geometry factor
+        env_names.append(['LaminaDamID[shape={},map={},k={}, cr={}]'.format(
+            env['shape'], files[int(own[q])], -dm.get('repr_k', dm['k']), dm.get('repr_cr', dm['contact_range']))
+            for q in range(S)])
+    elif dm is not None:
         cut = 1.0 - float(dm['contact_range'])
         abc = np.asarray(env['abc'], np.float64)
         e = len(envelopes)

@@ -5,6 +5,7 @@ config keys, runtime entries and output files, their per-locus / per-cluster loo
 the GPU kernels of this package (igm_amd.damid, .fish, .sprite, .polymer).
 
   DamidActivationDistanceStep  igm/steps/DamidActivationDistanceStep.py:125-346
+  NuclDamidActivationDistanceStep  igm/steps/NuclDamidActivationDistanceStep.py:120-360
   FishAssignmentStep           igm/steps/FishAssignmentStep.py:82-389
   SpriteAssignmentStep         igm/steps/SpriteAssignmentStep.py:20-263
   PolymerAssignmentStep        igm/steps/PolymerAssignmentStep.py:35-206
@@ -66,6 +67,32 @@ def _hip_damid(store, loci, pexp, plast, cfg, device):
                                        float(cr), shape, param, ctx=_lib.context(device), **kw)
 
 
+def _hip_nucldamid(store, loci, pexp, plast, cfg, device):
+    """NuclDamidActivationDistanceStep.task (py:222-287): the body's shape and parameters
+    come from model/restraints/nucleolus/*"""
+    from . import _lib, damid
+    from .steps import nucleolus_section
+    shape = rget(cfg, 'model/restraints/nucleolus/nucleus_shape')
+    xyz = np.ascontiguousarray(store.coordinates())
+    it_corr = int(cget(cfg, 'runtime/nuclDamID/iter_corr_knob', 1))
+    kw = {}
+    if shape == 'sphere':
+        param = rget(cfg, 'model/restraints/nucleolus/nucleus_radius')
+        cr = rget(cfg, 'restraints/nuclDamID/contact_range', 0.05)
+    elif shape == 'ellipsoid':
+        param = rget(cfg, 'model/restraints/nucleolus/nucleus_semiaxes')
+        cr = rget(cfg, 'restraints/nuclDamID/contact_range', 0.05)
+    elif shape == 'exp_map':  # get_damid_actdist_exp over the per-structure nucleolus maps (py:271-280)
+        nu = nucleolus_section(cfg, range(xyz.shape[1]))
+        param, cr = None, rget(cfg, 'restraints/nuclDamID/contact_range', 0.95)
+        kw = {'volumes': nu['volumes'], 'struct_map': nu['struct_map']}
+        shape = 'exp_map_nucl'
+    else:
+        raise NotImplementedError('NuclDamID restraint for shape %s has not been implemented yet.' % shape)
+    return damid.compute_damid_actdist(xyz, store.radii, store.copy_ptr, store.copy_idx, loci, pexp, plast, it_corr,
+                                       float(cr), shape, param, ctx=_lib.context(device), **kw)
+
+
 def _hip_fish(store, kind, items, tmin, tmax, device):
     from . import _lib, fish
     xyz = np.ascontiguousarray(store.coordinates())
@@ -89,10 +116,14 @@ def _hip_polymer(store, loci, edges, prob, rng, device):
 class DamidActivationDistanceStep(Step):
     """Lamina-DamID activation distances (DamidActivationDistanceStep.py:125-346)."""
 
+    SECTION = 'DamID'          # restraints/<SECTION>, runtime/<SECTION>
+    KERNEL = 'damid'           # the entry of steps.KERNELS[...]
+    TMP_DIR = 'damid_actdist'  # default restraints/<SECTION>/tmp_dir
+
     def __init__(self, cfg):
-        rt = _runtime(cfg, 'DamID')
+        rt = _runtime(cfg, self.SECTION)
         if 'sigma_list' not in rt:
-            rt['sigma_list'] = list(cfg['restraints']['DamID']['sigma_list'])
+            rt['sigma_list'] = list(cfg['restraints'][self.SECTION]['sigma_list'])
         if 'sigma' not in rt:
             rt['sigma'] = rt['sigma_list'].pop(0)
         if 'iter_corr_knob' not in rt:  # D1: optimization/iter_corr_knob is not in the schema, default 1
@@ -100,20 +131,21 @@ class DamidActivationDistanceStep(Step):
         super(DamidActivationDistanceStep, self).__init__(cfg)
 
     def name(self):
-        return 'DamidActivationDistanceStep (sigma={:.2f}%, iter={:s})'.format(
-            cget(self.cfg, 'runtime/DamID/sigma', -1) * 100.0, str(cget(self.cfg, 'runtime/opt_iter', 'N/A')))
+        return '{:s} (sigma={:.2f}%, iter={:s})'.format(
+            type(self).__name__, cget(self.cfg, 'runtime/%s/sigma' % self.SECTION, -1) * 100.0,
+            str(cget(self.cfg, 'runtime/opt_iter', 'N/A')))
 
     def _dir(self):
-        d = make_absolute_path(cget(self.cfg, 'restraints/DamID/tmp_dir', 'damid_actdist'),
+        d = make_absolute_path(cget(self.cfg, 'restraints/%s/tmp_dir' % self.SECTION, self.TMP_DIR),
                                cget(self.cfg, 'parameters/tmp_dir', 'tmp'))
         os.makedirs(d, exist_ok=True)
         return d
 
     def setup(self):
         from . import damid
-        sigma = cget(self.cfg, 'runtime/DamID/sigma')
-        profile = np.loadtxt(self.cfg['restraints']['DamID']['input_profile'], dtype='float32')
-        last = cget(self.cfg, 'runtime/DamID/damid_actdist_file', None)
+        sigma = cget(self.cfg, 'runtime/%s/sigma' % self.SECTION)
+        profile = np.loadtxt(self.cfg['restraints'][self.SECTION]['input_profile'], dtype='float32')
+        last = cget(self.cfg, 'runtime/%s/damid_actdist_file' % self.SECTION, None)
         last_rows = read_damid_rows(last) if last is not None and os.path.isfile(last) else None
         loci, pexp, plast = damid.select_loci(profile, sigma, last_rows)  # py:185-217
         bs = int(cget(self.cfg, 'optimization/kernel_opts/hip/locus_batch', 1 << 20))
@@ -128,7 +160,7 @@ class DamidActivationDistanceStep(Step):
     def task(self, batch, device):
         store = PopulationStore(self.cfg['optimization']['structure_output'])
         d = np.load(batch['in'])
-        rows = _kernel(self.cfg, 'damid')(store, d['loci'], d['pexp'], d['plast'], self.cfg, device)
+        rows = _kernel(self.cfg, self.KERNEL)(store, d['loci'], d['pexp'], d['plast'], self.cfg, device)
         tmp = batch['out'] + '.part.npy'
         np.save(tmp, rows)
         os.replace(tmp, batch['out'])
@@ -140,17 +172,28 @@ class DamidActivationDistanceStep(Step):
         rows = np.concatenate([np.load(b['out']) for b in self.argument_list]) if self.argument_list else \
             np.zeros(0, damid_row_dtype)
         out = os.path.join(self._dir(), 'damid_actdist.hdf5')
-        suffix = ['DamID_{:.4f}'.format(cget(self.cfg, 'runtime/DamID/sigma'))]
+        suffix = [self.SECTION + '_{:.4f}'.format(cget(self.cfg, 'runtime/%s/sigma' % self.SECTION))]
         if 'opt_iter' in self.cfg['runtime']:
             suffix.append('iter_{}'.format(self.cfg['runtime']['opt_iter'] - 1))
-        _rotate(cget(self.cfg, 'runtime/DamID/damid_actdist_file', None), out, suffix)
+        _rotate(cget(self.cfg, 'runtime/%s/damid_actdist_file' % self.SECTION, None), out, suffix)
         _write_h5(out, {'loc': np.ascontiguousarray(rows['loc'], np.int32),
                         'dist': np.ascontiguousarray(rows['dist'], np.float32),
                         'prob': np.ascontiguousarray(rows['prob'], np.float32)})
-        cset(self.cfg, 'runtime/DamID/damid_actdist_file', out)
+        cset(self.cfg, 'runtime/%s/damid_actdist_file' % self.SECTION, out)
 
     def skip(self):
-        cset(self.cfg, 'runtime/DamID/damid_actdist_file', os.path.join(self._dir(), 'damid_actdist.hdf5'))
+        cset(self.cfg, 'runtime/%s/damid_actdist_file' % self.SECTION,
+             os.path.join(self._dir(), 'damid_actdist.hdf5'))
+
+
+class NuclDamidActivationDistanceStep(DamidActivationDistanceStep):
+    """Nuclear-body DamID activation distances (NuclDamidActivationDistanceStep.py:120-360):
+    the lamina step on restraints/nuclDamID, measured against the nuclear body of
+    model/restraints/nucleolus/* instead of the nucleus."""
+
+    SECTION = 'nuclDamID'
+    KERNEL = 'nucldamid'
+    TMP_DIR = 'nucldamid_actdist'
 
 
 # ------------------------------------------------------------------ FISH
@@ -381,4 +424,5 @@ class PolymerAssignmentStep(Step):
              os.path.join(self._dir(), self.cfg['restraints']['polymer']['assignment_file']))
 
 
-KERNELS_HIP = {'damid': _hip_damid, 'fish': _hip_fish, 'sprite': _hip_sprite, 'polymer': _hip_polymer}
+KERNELS_HIP = {'damid': _hip_damid, 'nucldamid': _hip_nucldamid, 'fish': _hip_fish, 'sprite': _hip_sprite,
+               'polymer': _hip_polymer}

@@ -23,6 +23,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "exact_math.h"
+#include "exp_map_key.h"
 #include "igm_ctx.h"
 #include "mstep_common.h"
 
@@ -380,27 +381,17 @@ struct DamidExpArgs {
     igm_damid_row* rows;
 };
 
+// NUCL: the nuclear-body key of NuclDamidActivationDistanceStep.py:78-110 (shape 3), chosen
+// at compile time; everything after the key is shared
+template <bool NUCL>
 __device__ __forceinline__ double damid_exp_key(const DamidExpArgs& A, int bead, int s) {
     const igm::ms::VolMapDev m = A.maps[A.smap[s]];
     float p[3];
     load3(A.xyz, A.S, bead, s, p[0], p[1], p[2]);
-    long long v[3];
-    bool in = true;
-    for (int d = 0; d < 3; ++d) {
-        v[d] = (long long)rint(((double)p[d] - (double)m.origin[d]) / (double)m.grid[d]);
-        in = in && v[d] >= 0 && v[d] < m.n[d];
-    }
-    double t[3];
-    if (in) {
-        const int4 r = A.vox[m.off + (v[0] * m.n[1] + v[1]) * m.n[2] + v[2]];
-        const int e[3] = {r.x, r.y, r.z};
-        for (int d = 0; d < 3; ++d) t[d] = (double)p[d] - ((double)e[d] * (double)m.grid[d] + (double)m.origin[d]);
-    } else {
-        for (int d = 0; d < 3; ++d) t[d] = ((double)v[d] - (double)m.center[d]) * (double)m.grid[d];
-    }
-    return (t[0] * t[0] + t[2] * t[2]) + t[1] * t[1];
+    return igm::exp_map_key<NUCL>(p, m, A.vox);
 }
 
+template <bool NUCL>
 __global__ void __launch_bounds__(kBT) damid_exp_kernel(DamidExpArgs A) {
     const int q = blockIdx.x;
     if (q >= A.nloci) return;
@@ -416,7 +407,7 @@ __global__ void __launch_bounds__(kBT) damid_exp_kernel(DamidExpArgs A) {
     int cnt = 0;
     for (int ci = 0; ci < nc; ++ci) {
         const int bead = A.cidx[c0 + ci];
-        for (int s = threadIdx.x; s < S; s += kBT) cnt += damid_exp_key(A, bead, s) >= A.cr;
+        for (int s = threadIdx.x; s < S; s += kBT) cnt += damid_exp_key<NUCL>(A, bead, s) >= A.cr;
     }
     cnt = block_sum(cnt, sh_red);
     const int64_t nS = (int64_t)nc * S;
@@ -452,7 +443,7 @@ __global__ void __launch_bounds__(kBT) damid_exp_kernel(DamidExpArgs A) {
             for (int ci = 0; ci < nc; ++ci) {
                 const int bead = A.cidx[c0 + ci];
                 for (int s = threadIdx.x; s < S; s += kBT) {
-                    const unsigned long long u = (unsigned long long)__double_as_longlong(damid_exp_key(A, bead, s));
+                    const unsigned long long u = (unsigned long long)__double_as_longlong(damid_exp_key<NUCL>(A, bead, s));
                     if ((u & mask) == prefix) atomicAdd(&hist[(u >> shift) & 255ull], 1u);
                 }
             }
@@ -1233,10 +1224,10 @@ extern "C" int igm_damid_actdist(igm_ctx* c, uint32_t flags, const float* xyz, i
                                  int64_t* nrows_out) {
     if (!c) return IGM_E_INVALID;
     if (nbead <= 0 || nstruct <= 0 || nhap <= 0 || nloci < 0 || !xyz || !radii || !copy_ptr || !copy_idx ||
-        (nloci > 0 && (!loci || !p_exp || !plast)) || !nrows_out || (shape < 0 || shape > IGM_DAMID_EXP_MAP) ||
-        (shape != IGM_DAMID_EXP_MAP && !nucleus_param))
+        (nloci > 0 && (!loci || !p_exp || !plast)) || !nrows_out || (shape < 0 || shape > IGM_DAMID_EXP_MAP_NUCL) ||
+        (shape < IGM_DAMID_EXP_MAP && !nucleus_param))
         return fail(c, IGM_E_INVALID, "igm_damid_actdist: invalid arguments");
-    if (shape == IGM_DAMID_EXP_MAP && (c->vol_nmap <= 0 || (c->vol_nsmap > 0 && c->vol_nsmap != nstruct)))
+    if (shape >= IGM_DAMID_EXP_MAP && (c->vol_nmap <= 0 || (c->vol_nsmap > 0 && c->vol_nsmap != nstruct)))
         return fail(c, IGM_E_INVALID,
                     "igm_damid_actdist: exp_map needs maps staged by igm_mstep_set_volumes with one map index per "
                     "structure (%d staged, %d structures)", c->vol_nsmap, nstruct);
@@ -1299,7 +1290,7 @@ extern "C" int igm_damid_actdist(igm_ctx* c, uint32_t flags, const float* xyz, i
     }
     igm_damid_row* d_rows;
     IGM_TRY(out_device(c, flags, "dm_rows", rows, (size_t)total, &d_rows));
-    if (shape == IGM_DAMID_EXP_MAP) {
+    if (shape >= IGM_DAMID_EXP_MAP) {
         DamidExpArgs E;
         E.xyz = d_xyz;
         E.S = nstruct;
@@ -1328,7 +1319,10 @@ extern "C" int igm_damid_actdist(igm_ctx* c, uint32_t flags, const float* xyz, i
         E.rows = d_rows;
         {
             Timed tm(c, "damid");
-            hipLaunchKernelGGL(damid_exp_kernel, dim3((unsigned)nloci), dim3(kBT), 0, c->stream, E);
+            if (shape == IGM_DAMID_EXP_MAP_NUCL)
+                hipLaunchKernelGGL(damid_exp_kernel<true>, dim3((unsigned)nloci), dim3(kBT), 0, c->stream, E);
+            else
+                hipLaunchKernelGGL(damid_exp_kernel<false>, dim3((unsigned)nloci), dim3(kBT), 0, c->stream, E);
             IGM_HIP_CHECK(c, hipGetLastError());
         }
         IGM_TRY(to_host(c, flags, rows, d_rows, (size_t)total));

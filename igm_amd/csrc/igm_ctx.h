@@ -23,6 +23,10 @@ struct igm_ctx {
     // volumetric maps staged by igm_mstep_set_volumes (device copies live in ws slots
     // "vol_maps", "vol_vox", "vol_smap")
     int vol_nmap = 0, vol_nsmap = 0;
+    // host copies of the default table and of the per-envelope tables of
+    // igm_mstep_set_envelope_maps (empty: envelope e reads the default table)
+    std::vector<int> vol_smap_h;
+    std::vector<int> vol_emap_h[IGM_MAX_ENVELOPES];
     int num_cus = 256;
     // last HBM-size anneal: {K, slots, builds, re-cuts, largest resident set, largest
     // owned set, abort (0: the domain-decomposed engine ran; -1 / > 0: the population
@@ -142,6 +146,46 @@ struct Timed {
 };
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// Device table of the map index that volume envelope e reads for structure s of a call
+// over nstruct structures: table[e * stride + s] (table NULL: map 0).  Without a table of
+// igm_mstep_set_envelope_maps this is the default struct_map of igm_mstep_set_volumes with
+// stride 0 -- the lookup of a library without per-envelope tables; otherwise one row per
+// envelope (its own table, else the default one, else zeros), staged in "vol_etab".
+// A staged table must cover the structures of the call.
+inline int envelope_map_tables(igm_ctx* c, int nstruct, const int** table, int* stride) {
+    *table = nullptr;
+    *stride = 0;
+    bool own = false;
+    for (int e = 0; e < IGM_MAX_ENVELOPES; ++e) {
+        const int n = (int)c->vol_emap_h[e].size();
+        if (n > 0 && n < nstruct)
+            return fail(c, IGM_E_INVALID, "volume map index of envelope %d staged for %d structures, batch has %d", e,
+                        n, nstruct);
+        own = own || n > 0;
+    }
+    if (c->vol_nsmap > 0 && c->vol_nsmap < nstruct)
+        return fail(c, IGM_E_INVALID, "volume map index staged for %d structures, batch has %d", c->vol_nsmap, nstruct);
+    void* ps;
+    if (!own) {
+        if (c->vol_nsmap > 0) {
+            IGM_TRY(workspace(c, "vol_smap", 1, &ps));
+            *table = (const int*)ps;
+        }
+        return IGM_OK;
+    }
+    std::vector<int> tab((size_t)IGM_MAX_ENVELOPES * nstruct, 0);
+    for (int e = 0; e < IGM_MAX_ENVELOPES; ++e) {
+        const std::vector<int>& src = c->vol_emap_h[e].empty() ? c->vol_smap_h : c->vol_emap_h[e];
+        for (int s = 0; s < nstruct && s < (int)src.size(); ++s) tab[(size_t)e * nstruct + s] = src[s];
+    }
+    IGM_TRY(workspace(c, "vol_etab", sizeof(int) * tab.size(), &ps));
+    IGM_HIP_CHECK(c, hipMemcpyAsync(ps, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, c->stream));
+    IGM_HIP_CHECK(c, hipStreamSynchronize(c->stream));  // tab dies here
+    *table = (const int*)ps;
+    *stride = nstruct;
+    return IGM_OK;
+}
 
 // at least n auxiliary streams; the work on them is forked from and joined into c->stream
 inline int aux_streams(igm_ctx* c, int n) {

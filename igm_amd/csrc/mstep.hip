@@ -811,7 +811,7 @@ __device__ __forceinline__ void env_terms(int s, T xi, T yi, T zi, T ri, uint32_
         double en = 0.0;
         if (P.env_kind[e] == IGM_ENV_VOLUME) {
             const T kk = std::is_same<T, float>::value ? (T)P.env_k[e] : (T)P.env_k_d[e];
-            volume_term<T, EN>(xi, yi, zi, P.vmaps[P.vsmap ? P.vsmap[s] : 0], P.vvox, envf, kk, fx, fy, fz, en);
+            volume_term<T, EN>(xi, yi, zi, P.vmaps[vol_map_index(P, e, s)], P.vvox, envf, kk, fx, fy, fz, en);
         } else if constexpr (std::is_same<T, float>::value)
             envelope_term<T, EN>(xi, yi, zi, rad, P.env_abc[e][0] * envf, P.env_abc[e][1] * envf,
                                  P.env_abc[e][2] * envf, P.env_k[e], fx, fy, fz, en);
@@ -2688,7 +2688,7 @@ __device__ __forceinline__ void pop_slot_force(const PopArgs& A, int s, int i, s
         if (!(fl & (IGM_ATOM_ENV0 << e))) continue;
         if (A.P.env_kind[e] == IGM_ENV_VOLUME) {
             double en = 0.0;
-            volume_term<float, false>(xi, yi, zi, A.P.vmaps[A.P.vsmap ? A.P.vsmap[s] : 0], A.P.vvox, envf,
+            volume_term<float, false>(xi, yi, zi, A.P.vmaps[vol_map_index(A.P, e, s)], A.P.vvox, envf,
                                       A.P.env_k[e], fx, fy, fz, en);
             continue;
         }
@@ -3534,7 +3534,7 @@ static double f32_as_printed(float f) {
     return (double)f;
 }
 
-int make_devparams(igm_ctx* c, const igm_mstep_params* prm, int natom, const float* d_radii,
+int make_devparams(igm_ctx* c, const igm_mstep_params* prm, int nstruct, int natom, const float* d_radii,
                    const uint32_t* d_flags, DevParams* P, const int** d_atype) {
     // host copies of radii/flags: max bead radius and the atom types
     std::vector<float> r(natom);
@@ -3547,6 +3547,7 @@ int make_devparams(igm_ctx* c, const igm_mstep_params* prm, int natom, const flo
         if ((fl[i] & IGM_ATOM_BEAD) && r[i] > rmax) rmax = r[i];
     memset(P, 0, sizeof(*P));
     P->nenv = prm->nenvelopes;
+    bool any_volume = false;
     if (P->nenv < 0 || P->nenv > IGM_MAX_ENVELOPES) return fail(c, IGM_E_INVALID, "nenvelopes out of range");
     for (int e = 0; e < P->nenv; ++e) {
         for (int d = 0; d < 3; ++d) {
@@ -3562,18 +3563,15 @@ int make_devparams(igm_ctx* c, const igm_mstep_params* prm, int natom, const flo
             if (c->vol_nmap <= 0)
                 return fail(c, IGM_E_INVALID, "envelope %d is volumetric but no map was staged (igm_mstep_set_volumes)",
                             e);
-            void *pm, *pv, *ps;
+            void *pm, *pv;
             IGM_TRY(workspace(c, "vol_maps", 1, &pm));
             IGM_TRY(workspace(c, "vol_vox", 1, &pv));
             P->vmaps = (const VolMapDev*)pm;
             P->vvox = (const int4*)pv;
-            P->vsmap = nullptr;
-            if (c->vol_nsmap > 0) {
-                IGM_TRY(workspace(c, "vol_smap", 1, &ps));
-                P->vsmap = (const int*)ps;
-            }
+            any_volume = true;
         }
     }
+    if (any_volume) IGM_TRY(envelope_map_tables(c, nstruct, &P->vsmap, &P->vstride));  // once per call
     // Verlet skin: LAMMPS 'neighbor maxrad bin' uses skin = maxrad.  The skin only sets
     // how often the (always complete) list is rebuilt, not the forces; 0.7 maxrad is the
     // measured optimum on MI355X (scripts/gpu_skin.sh: fewer list entries per force
@@ -3658,6 +3656,8 @@ int set_volumes(igm_ctx* c, int32_t nmap, const igm_volume_map* maps, const int3
     IGM_HIP_CHECK(c, hipSetDevice(c->device));
     c->vol_nmap = 0;
     c->vol_nsmap = 0;
+    c->vol_smap_h.clear();
+    for (int e = 0; e < IGM_MAX_ENVELOPES; ++e) c->vol_emap_h[e].clear();
     if (nmap == 0) return IGM_OK;
     std::vector<VolMapDev> hm(nmap);
     long long tot = 0;
@@ -3700,9 +3700,25 @@ int set_volumes(igm_ctx* c, int32_t nmap, const igm_volume_map* maps, const int3
         IGM_TRY(workspace(c, "vol_smap", sizeof(int) * nstruct, &ps));
         IGM_HIP_CHECK(c, hipMemcpyAsync(ps, struct_map, sizeof(int) * nstruct, hipMemcpyHostToDevice, c->stream));
         c->vol_nsmap = nstruct;
+        c->vol_smap_h.assign(struct_map, struct_map + nstruct);
     }
     IGM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
     c->vol_nmap = nmap;
+    return IGM_OK;
+}
+
+// the map index per structure that envelope `env` reads instead of the default table
+int set_envelope_maps(igm_ctx* c, int32_t env, const int32_t* env_map, int32_t nstruct) {
+    if (env < 0 || env >= IGM_MAX_ENVELOPES || (env_map && nstruct <= 0))
+        return fail(c, IGM_E_INVALID, "igm_mstep_set_envelope_maps: invalid arguments");
+    c->vol_emap_h[env].clear();
+    if (!env_map) return IGM_OK;
+    if (c->vol_nmap <= 0)
+        return fail(c, IGM_E_INVALID, "igm_mstep_set_envelope_maps: no map staged (igm_mstep_set_volumes)");
+    for (int s = 0; s < nstruct; ++s)
+        if (env_map[s] < 0 || env_map[s] >= c->vol_nmap)
+            return fail(c, IGM_E_INVALID, "igm_mstep_set_envelope_maps: env_map[%d] = %d", s, env_map[s]);
+    c->vol_emap_h[env].assign(env_map, env_map + nstruct);  // staged with the next igm_mstep_* call
     return IGM_OK;
 }
 
@@ -3711,10 +3727,6 @@ int prepare(igm_ctx* c, uint32_t flags, const igm_mstep_params* prm, int32_t nst
             const float* radii, const uint32_t* atom_flags, const igm_bond* shared_bonds, int64_t nshared,
             const int64_t* sbond_ptr, const igm_bond* sbonds, Prepared* out) {
     if (natom <= 0 || natom > 65535) return fail(c, IGM_E_UNSUPPORTED, "natom=%d outside [1, 65535]", natom);
-    for (int e = 0; e < prm->nenvelopes && e < IGM_MAX_ENVELOPES; ++e)
-        if (prm->env_kind[e] == IGM_ENV_VOLUME && c->vol_nsmap > 0 && c->vol_nsmap < nstruct)
-            return fail(c, IGM_E_INVALID, "volume map index staged for %d structures, batch has %d", c->vol_nsmap,
-                        nstruct);
     const float* d_radii;
     const uint32_t* d_flags;
     const igm_bond* d_shared;
@@ -3751,7 +3763,7 @@ int prepare(igm_ctx* c, uint32_t flags, const igm_mstep_params* prm, int32_t nst
     if (!sbond_ptr) d_sptr = nullptr;
     DevParams P;
     const int* d_atype;
-    IGM_TRY(make_devparams(c, prm, natom, d_radii, d_flags, &P, &d_atype));
+    IGM_TRY(make_devparams(c, prm, nstruct, natom, d_radii, d_flags, &P, &d_atype));
     const int nslice = P.nslice;
     void *p_deg, *p_fill, *p_soff, *p_size, *p_base, *p_nt, *p_tb, *p_err, *p_wc;
     IGM_TRY(workspace(c, "ms_deg", sizeof(int) * (size_t)nstruct * natom, &p_deg));
@@ -3887,7 +3899,7 @@ PopArgs pop_view(const PopArgs& Q, int s0, int ns, int g) {
     V.cm.bonds.deg = Q.cm.bonds.deg + (size_t)s0 * Q.cm.natom;
     V.cm.bonds.tbase = Q.cm.bonds.tbase + s0;
     V.cm.bonds.ntype = Q.cm.bonds.ntype + s0;
-    if (V.P.vsmap) V.P.vsmap = Q.P.vsmap + s0;
+    if (V.P.vsmap) V.P.vsmap = Q.P.vsmap + s0;  // every row keeps its stride
     for (int b = 0; b < 2; ++b)
         V.buf[b] = PopBuf{Q.buf[b].pos + o, Q.buf[b].vel + o, Q.buf[b].frc + o, Q.buf[b].aid + o, Q.buf[b].slot + o,
                         Q.buf[b].flg + o};
@@ -4729,6 +4741,11 @@ extern "C" int igm_mstep_set_volumes(igm_ctx* c, int32_t nmap, const igm_volume_
                                      const int32_t* struct_map, int32_t nstruct) {
     if (!c) return IGM_E_INVALID;
     return set_volumes(c, nmap, maps, struct_map, nstruct);
+}
+
+extern "C" int igm_mstep_set_envelope_maps(igm_ctx* c, int32_t env, const int32_t* env_map, int32_t nstruct) {
+    if (!c) return IGM_E_INVALID;
+    return set_envelope_maps(c, env, env_map, nstruct);
 }
 
 /* Profiling aid (IGM_PROF=1 in the environment): cycle counters of the last LDS-path

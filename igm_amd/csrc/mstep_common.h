@@ -38,7 +38,7 @@ struct DevParams {
     int env_kind[IGM_MAX_ENVELOPES];  // IGM_ENV_ELLIPSOID / IGM_ENV_VOLUME
     const VolMapDev* vmaps;           // volume maps (igm_mstep_set_volumes)
     const int4* vvox;
-    const int* vsmap;                 // map of structure s (NULL: map 0)
+    const int* vsmap;                 // envelope e reads map vsmap[e * vstride + s] (NULL: map 0)
     float env_abc[IGM_MAX_ENVELOPES][3];
     float env_k[IGM_MAX_ENVELOPES];
     double env_abc_d[IGM_MAX_ENVELOPES][3];
@@ -55,7 +55,16 @@ struct DevParams {
     int ntype;
     const double2* pair_tab;
     const double* rtype;
+    // row stride of vsmap: 0 = one table for every envelope (igm_mstep_set_volumes'
+    // struct_map), nstruct = one row per envelope (igm_mstep_set_envelope_maps).  Kept
+    // behind the fields the MD kernels read, whose offsets stay as they were.
+    int vstride;
 };
+
+// map of volume envelope e for structure s (vstride 0: the one default table)
+__device__ __forceinline__ int vol_map_index(const DevParams& P, int e, int s) {
+    return P.vsmap ? P.vsmap[e * P.vstride + s] : 0;
+}
 
 // ------------------------------------------------------------- reductions
 #ifndef IGM_DPP_REDUCE

@@ -57,7 +57,8 @@ struct VArgs {
     int env_kind[IGM_MAX_ENVELOPES];
     const igm::ms::VolMapDev* vmaps;       // volume maps (igm_mstep_set_volumes)
     const int4* vvox;
-    const int* vsmap;
+    const int* vsmap;  // envelope e reads map vsmap[e * vstride + s] (NULL: map 0)
+    int vstride;
     double tol;
     int64_t* stats;
 };
@@ -132,7 +133,7 @@ __global__ void __launch_bounds__(256) violations_kernel(VArgs A) {
             if (!(A.aflags[(size_t)s * A.afs + a] & (IGM_ATOM_ENV0 << e))) continue;
             const float* p = x + 3 * a;
             if (A.env_kind[e] == IGM_ENV_VOLUME) {
-                record(he, volume_score(p, A.vmaps[A.vsmap ? A.vsmap[s] : 0], A.vvox, A.env_k[e], A.env_scale[e]),
+                record(he, volume_score(p, A.vmaps[A.vsmap ? A.vsmap[e * A.vstride + s] : 0], A.vvox, A.env_k[e], A.env_scale[e]),
                        A.tol);
                 continue;
             }
@@ -181,6 +182,7 @@ extern "C" int igm_mstep_violations(igm_ctx* c, uint32_t flags, const igm_mstep_
     A.nshared = nshared;
     A.tol = tol;
     for (int k = 0; k < nclass_bonds; ++k) A.class_cr[k] = class_cr[k];
+    bool any_volume = false;
     for (int e = 0; e < A.nenv; ++e) {
         for (int d = 0; d < 3; ++d) A.env_abc[e][d] = prm->env_semiaxes[e][d];
         A.env_k[e] = prm->env_k[e];
@@ -190,20 +192,15 @@ extern "C" int igm_mstep_violations(igm_ctx* c, uint32_t flags, const igm_mstep_
         if (A.env_kind[e] == IGM_ENV_VOLUME) {
             if (!env_scale) A.env_scale[e] = 0.95;  // GenEnvelope's contact_range (genenvelope.py:48-58)
             if (c->vol_nmap <= 0) return fail(c, IGM_E_INVALID, "igm_mstep_violations: no volume map staged");
-            if (c->vol_nsmap > 0 && c->vol_nsmap < nstruct)
-                return fail(c, IGM_E_INVALID, "igm_mstep_violations: volume map index staged for %d structures",
-                            c->vol_nsmap);
-            void *pm, *pv, *ps;
+            void *pm, *pv;
             IGM_TRY(workspace(c, "vol_maps", 1, &pm));
             IGM_TRY(workspace(c, "vol_vox", 1, &pv));
             A.vmaps = (const igm::ms::VolMapDev*)pm;
             A.vvox = (const int4*)pv;
-            if (c->vol_nsmap > 0) {
-                IGM_TRY(workspace(c, "vol_smap", 1, &ps));
-                A.vsmap = (const int*)ps;
-            }
+            any_volume = true;
         }
     }
+    if (any_volume) IGM_TRY(envelope_map_tables(c, nstruct, &A.vsmap, &A.vstride));  // once per call
     int64_t nsb = 0;
     if (sbond_ptr) {
         if (flags & IGM_DEVICE_PTRS) {

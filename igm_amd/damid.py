@@ -8,8 +8,8 @@ Mirrors igm/steps/DamidActivationDistanceStep.py:
                             the "%6d %.5f %.5f" text round trip of task()/reduce():
                             bit-exact rows {loc, dist, prob}.
   * get_damid_actdist_I  -- the per-locus function signature (py:376).
-Shapes 'sphere' and 'ellipsoid' are supported; 'exp_map' (volumetric maps read from
-files) is out of scope.  Unlike the reference's task(), the
+Shapes 'sphere', 'ellipsoid' and 'exp_map' (volumetric maps) are supported, and
+'exp_map_nucl', the exp_map form of NuclDamidActivationDistanceStep.  Unlike the reference's task(), the
 ellipsoid really is computed (the reference tests `'shape' == 'ellipsoid'`, a string
 literal, so an ellipsoid run emits no rows: defect D3, py:258).
 No CPU fallback: every row comes from libigmhip.so.
@@ -23,7 +23,8 @@ from ._lib import damid_row_dtype, result_dtype
 
 damid_actdist_shape = [('loc', 'int32'), ('dist', 'float32'), ('prob', 'float32')]
 damid_actdist_fmt_str = "%6d %.5f %.5f"
-SHAPES = {'sphere': 0, 'ellipsoid': 1, 'exp_map': 2}
+# 'exp_map_nucl': the nuclear-body key of NuclDamidActivationDistanceStep.py:78-110 (shape 3)
+SHAPES = {'sphere': 0, 'ellipsoid': 1, 'exp_map': 2, 'exp_map_nucl': 3}
 
 
 def select_loci(profile, sigma, last_rows=None):
@@ -42,7 +43,7 @@ def select_loci(profile, sigma, last_rows=None):
 def _nucleus_param(shape, nucleus_param):
     if shape not in SHAPES:
         raise NotImplementedError('DamID restraint for shape %s has not been implemented yet.' % shape)
-    if shape == 'exp_map':
+    if shape in ('exp_map', 'exp_map_nucl'):
         return np.zeros(3, np.float64)
     if shape == 'sphere':
         return np.array([float(np.ravel(nucleus_param)[0])] * 3, np.float64)
@@ -59,9 +60,10 @@ def compute_damid_actdist(xyz, radii, copy_ptr, copy_idx, loci, p_exp, plast, it
     batches).  xyz: (nbead, nstruct, 3) float32 bead-major (the .hss layout).
     shape 'exp_map' (get_damid_actdist_exp, py:475-577): `volumes` are the VolumeFile
     maps (igm_amd.volume.read_volume) and struct_map[s] the map of structure s
-    (volumes_idx); they are staged into the context."""
+    (volumes_idx); they are staged into the context.  shape 'exp_map_nucl' is the same
+    step with the voxel-to-voxel distance of NuclDamidActivationDistanceStep.py:78-110."""
     c = ctx or _lib.context(device)
-    if shape == 'exp_map':
+    if shape in ('exp_map', 'exp_map_nucl'):
         from . import volume as V
         if volumes is None:
             raise ValueError('exp_map needs the volume maps')

@@ -4,17 +4,21 @@ up with an acceptable violation score, or max_iterations unsuccessful iterations
 
   start-up   starting_coordinates copied, or RandomInit [+ PolymerAssignmentStep when
              the chain is modelled by distance distributions] + RelaxInit (:50-82)
-  iteration  PolymerAssignmentStep (restraints/polymer), ActivationDistanceStep
-             (Hi-C), FishAssignmentStep (FISH), SpriteAssignmentStep (sprite),
-             DamidActivationDistanceStep (DamID), ModelingStep (:105-167), in that order
+  iteration  PolymerAssignmentStep (restraints/polymer), NuclDamidActivationDistanceStep
+             (nuclDamID), ActivationDistanceStep (Hi-C), FishAssignmentStep (FISH),
+             SpriteAssignmentStep (sprite), DamidActivationDistanceStep (DamID),
+             ModelingStep (:105-167), in that order
   control    is_acceptable = runtime/violation_score < optimization/max_violations;
              the threshold lists advance together when acceptable and no further
              iteration is forced (min_iterations, force_last_iteration,
              force_minimum_iterations_hic_cutoff), else opt_iter += 1 (:169-325)
 
-Unsupported sections (tracing, nuclDamID, nucleolus) raise where the reference would
-run them.  Preprocess (genome/index, .hss allocation) is the caller's: the population
-file must exist.  No email notifications, no control socket.
+The nucleolus exclusion body (model/restraints/nucleolus) needs no A-step; it and
+nuclDamID are modelled on an exp_map nucleus only (ModelingStep raises otherwise, as
+the reference fails there).  The unsupported section (tracing: the reference has no
+A-step for it) raises where the reference would run it.  Preprocess (genome/index,
+.hss allocation) is the caller's: the population file must exist.  No email
+notifications, no control socket.
 """
 import os
 import shutil
@@ -42,12 +46,13 @@ def startup_steps(cfg):
 def iteration_steps(cfg):
     """bin/igm-run:105-161"""
     R = cfg.get('restraints', {})
-    for key in ('nuclDamID', 'tracing'):
-        if key in R:
-            raise NotImplementedError('restraints/%s is not implemented on the hip kernel' % key)
+    if 'tracing' in R:
+        raise NotImplementedError('restraints/tracing is not implemented on the hip kernel')
     steps = []
     if 'polymer' in R:
         steps.append(ST.PolymerAssignmentStep)
+    if 'nuclDamID' in R:  # bin/igm-run:118-119
+        steps.append(ST.NuclDamidActivationDistanceStep)
     if 'Hi-C' in R:
         steps.append(ST.ActivationDistanceStep)
     if 'FISH' in R:
@@ -87,9 +92,10 @@ def run_pipeline(cfg, on_iteration=None):
             len(ST.cget(cfg, 'runtime/Hi-C/intra_sigma_list', [])) != 0 or
             len(ST.cget(cfg, 'runtime/Hi-C/inter_sigma_list', [])) != 0)
         damid_inc = _remaining(cfg, 'DamID', 'sigma_list')
+        nucldamid_inc = _remaining(cfg, 'nuclDamID', 'sigma_list')  # bin/igm-run:196-199
         fish_inc = _remaining(cfg, 'FISH', 'tol_list')
         sprite_inc = _remaining(cfg, 'sprite', 'volume_fraction_list')
-        all_done = not (hic_inc or damid_inc or fish_inc or sprite_inc)
+        all_done = not (hic_inc or damid_inc or nucldamid_inc or fish_inc or sprite_inc)
         force = (opt_iter < min_iter - 1) and (opt_iter != 0)
         if ST.cget(cfg, 'optimization/force_last_iteration', False) and all_done and opt_iter == 0:
             force = True
@@ -104,6 +110,9 @@ def run_pipeline(cfg, on_iteration=None):
                 opt_iter = 0
             if damid_inc:
                 del rt['DamID']['sigma']
+                opt_iter = 0
+            if nucldamid_inc:  # bin/igm-run:265-269
+                del rt['nuclDamID']['sigma']
                 opt_iter = 0
             if fish_inc:
                 del rt['FISH']['tol']

@@ -60,6 +60,32 @@ def damid_envelope_flags(xyz, radii, rows, semiaxes, contact_range, env_index, b
     return out, nsel
 
 
+def volume_envelope_flags(xyz, rows, struct_map, env_index, base_flags, ctx=None, device=0):
+    """GenDamid._apply_envelope membership (gendamid.py:17-47,101-107) on the maps
+    staged in the context (igm_volume_select): (S, N) flags = base_flags | ENV bit of
+    envelope `env_index` for the beads of each structure with snormsq_exp < d**2, and the
+    rows selected per structure.  struct_map: (S,) index into the staged maps, or None
+    for the default table.  base_flags: (N,), or (S, N) -- the result of an earlier
+    selection, so that selections compose on one array."""
+    c = ctx or _lib.context(device)
+    xyz = np.ascontiguousarray(xyz, np.float32)
+    S, N = xyz.shape[0], xyz.shape[1]
+    base = np.ascontiguousarray(base_flags, np.uint32)
+    assert base.shape in ((N,), (S, N))
+    r = np.zeros(len(rows), damid_row_dtype)
+    if len(rows):
+        r['loc'], r['dist'], r['prob'] = rows['loc'], rows['dist'], rows['prob']
+    smap = None if struct_map is None else np.ascontiguousarray(struct_map, np.int32)
+    assert smap is None or smap.shape == (S,)
+    out = np.zeros((S, N), np.uint32)
+    nsel = np.zeros(S, np.int32)
+    rc = c.lib.igm_volume_select(c.h, 0, S, N, xyz.ctypes.data, r.ctypes.data if len(r) else None, len(r),
+                                 smap.ctypes.data if smap is not None else None, int(IGM_ATOM_ENV0 << env_index),
+                                 base.ctypes.data, int(base.ndim == 2), out.ctypes.data, nsel.ctypes.data)
+    c.check(rc, 'igm_volume_select')
+    return out, nsel
+
+
 def _copies(copy_ptr, copy_idx, h):
     return copy_idx[copy_ptr[h]:copy_ptr[h + 1]]
 

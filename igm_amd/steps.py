@@ -506,20 +506,52 @@ def envelope_section(cfg, sids):
     raise NotImplementedError('Envelope (%s) not implemented' % shape)
 
 
+def nucleolus_section(cfg, sids):
+    """model/restraints/nucleolus as an assemble spec (ModelingStep.py:306-323): the
+    GenEnvelope of map prefix + str(volumes_idx[sid % len]) + '.bin' per structure"""
+    prefix = rget(cfg, 'model/restraints/nucleolus/volume_prefix')
+    idx = rget(cfg, 'model/restraints/nucleolus/volumes_idx')
+    k = rget(cfg, 'model/restraints/nucleolus/nucleus_kspring')
+    files = [prefix + str(idx[int(s) % len(idx)]) + '.bin' for s in sids]
+    uniq = sorted(set(files))
+    return {'shape': rget(cfg, 'model/restraints/nucleolus/nucleus_shape'), 'k': float(k), 'repr_k': k, 'files': uniq,
+            'volumes': [_body_volume(f, uniq) for f in uniq],
+            'struct_map': np.array([uniq.index(f) for f in files], np.int32)}
+
+
+_BODY_VOLUMES = {}
+
+
+def _body_volume(path, keep):
+    """the nucleolus maps of the section, read once each (the nucleus cache above is left
+    alone); entries of files the section no longer names are dropped"""
+    from . import volume as V
+    for k in [k for k in _BODY_VOLUMES if k[0] not in keep]:
+        del _BODY_VOLUMES[k]
+    key = (path, os.path.getmtime(path))
+    if key not in _BODY_VOLUMES:
+        _BODY_VOLUMES[key] = V.read_volume(path)
+    return _BODY_VOLUMES[key]
+
+
 def modeling_spec(cfg, sids):
     """Everything ModelingStep.task adds to a structure (ModelingStep.py:213-503) for the
     structures `sids`, as an igm_amd.assemble spec.  Sections this layer does not
     implement raise NotImplementedError -- none is dropped silently."""
     rs = cget(cfg, 'model/restraints', {}) or {}
     R = cfg.get('restraints', {}) or {}
-    for key in ('tracing', 'nuclDamID'):
-        if key in R:
-            raise NotImplementedError('restraints/%s is not implemented on the hip kernel' % key)
-    if 'nucleolus' in rs:
-        # ModelingStep.py:306-327: GenEnvelope of a second map; the reference logs an
-        # undefined name unless the envelope is exp_map (D8), and one structure would need
-        # two maps -- not supported by igm_mstep_set_volumes
-        raise NotImplementedError('model/restraints/nucleolus is not implemented on the hip kernel')
+    if 'tracing' in R:  # the reference has no A-step for it (bin/igm-run:122-136)
+        raise NotImplementedError('restraints/tracing is not implemented on the hip kernel')
+    if 'nucleolus' in rs or 'nuclDamID' in R:
+        # ModelingStep.py:306-371 runs only on an exp_map nucleus: it logs an undefined name
+        # (:326) and adds an undefined restraint (:347-370) otherwise (D8).  Checked before
+        # any key of the sections is read.
+        shape = cget(cfg, 'model/restraints/envelope/nucleus_shape')
+        if shape != 'exp_map':
+            raise NotImplementedError('model/restraints/nucleolus and restraints/nuclDamID need nucleus_shape '
+                                      'exp_map (the reference fails on %r)' % shape)
+        if 'nucleolus' not in rs:
+            raise NotImplementedError('restraints/nuclDamID needs the maps of model/restraints/nucleolus')
     spec = {'evfactor': float(rget(cfg, 'model/restraints/excluded/evfactor')),
             'protocol': cfg['optimization']['optimizer_options']}
     if 'polymer' in rs:
@@ -540,10 +572,17 @@ def modeling_spec(cfg, sids):
         spec['hic'] = {'rows': read_rows(act) if act else np.zeros(0, row_dtype),
                        'contact_range': float(rget(cfg, 'restraints/Hi-C/contact_range', 2.0)),
                        'k': float(rget(cfg, 'restraints/Hi-C/contact_kspring', 0.05))}
+    if 'nucleolus' in rs:
+        spec['nucleolus'] = nucleolus_section(cfg, sids)
+    if 'nuclDamID' in R:  # ModelingStep.py:331-371
+        cr = rget(cfg, 'restraints/nuclDamID/contact_range', 2.0)
+        k = rget(cfg, 'restraints/nuclDamID/contact_kspring', 0.05)
+        spec['nucldamid'] = {'rows': read_damid_rows(cget(cfg, 'runtime/nuclDamID/damid_actdist_file')),
+                             'contact_range': float(cr), 'k': float(k), 'repr_cr': cr, 'repr_k': k}
     if 'DamID' in R:
+        cr, k = rget(cfg, 'restraints/DamID/contact_range', 2.0), rget(cfg, 'restraints/DamID/contact_kspring', 0.05)
         spec['damid'] = {'rows': read_damid_rows(cget(cfg, 'runtime/DamID/damid_actdist_file')),
-                         'contact_range': float(rget(cfg, 'restraints/DamID/contact_range', 2.0)),
-                         'k': float(rget(cfg, 'restraints/DamID/contact_kspring', 0.05))}
+                         'contact_range': float(cr), 'k': float(k), 'repr_cr': cr, 'repr_k': k}
     if 'sprite' in R:
         a = _h5_tree(sprite_assignment_path(cfg))
         spec['sprite'] = {'assignment': a['assignment'], 'indptr': a['indptr'], 'selected': a['selected'],
@@ -734,7 +773,8 @@ class ModelingStep(Step):
 
 
 # ------------------------------------------------------------------ the other steps
-from .assign_steps import (DamidActivationDistanceStep, FishAssignmentStep, PolymerAssignmentStep,  # noqa: E402
+from .assign_steps import (DamidActivationDistanceStep, FishAssignmentStep,  # noqa: E402
+                           NuclDamidActivationDistanceStep, PolymerAssignmentStep,
                            SpriteAssignmentStep, KERNELS_HIP as _A_HIP)
 from .init_steps import RandomInit, RelaxInit, KERNELS_HIP as _I_HIP  # noqa: E402
 

@@ -8,6 +8,8 @@
                                  (100 nm grid)
   stage                       -- igm_mstep_set_volumes: the maps and the per-structure
                                  map index volumes_idx[sid % len] (ModelingStep.py:265-270)
+  set_envelope_maps           -- igm_mstep_set_envelope_maps: one envelope's own map index
+                                 per structure (a nucleolus beside the nucleus map)
 """
 import ctypes
 import struct
@@ -80,3 +82,12 @@ def stage(ctx, vols, struct_map=None):
                                        0 if smap is None else len(smap))
     ctx.check(rc, 'igm_mstep_set_volumes')
     ctx._volumes = (arr, keep, smap)
+
+
+def set_envelope_maps(ctx, env, env_map):
+    """igm_mstep_set_envelope_maps: envelope `env` reads map env_map[s] of the staged
+    pool for structure s (None: back to the default table of stage())."""
+    emap = None if env_map is None else np.ascontiguousarray(env_map, np.int32)
+    rc = ctx.lib.igm_mstep_set_envelope_maps(ctx.h, int(env), emap.ctypes.data if emap is not None else None,
+                                             0 if emap is None else len(emap))
+    ctx.check(rc, 'igm_mstep_set_envelope_maps')

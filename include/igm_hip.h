@@ -113,10 +113,15 @@ int igm_astep_update_plast(igm_ctx* ctx, uint32_t flags, igm_pair* pairs, int64_
 /* shape 2 = exp_map: get_damid_actdist_exp (:475-577) with snormsq_exp (:79-115) on the
  * volumetric maps staged by igm_mstep_set_volumes (struct_map = the map of every
  * structure, volumes_idx); distances ascending, pnow = count(d^2 >= contact_range),
- * dist 1e-9 when p <= 0 (nucleus_param and radii unused). */
+ * dist 1e-9 when p <= 0 (nucleus_param and radii unused).
+ * shape 3 = the nuclear-body form of the same step: get_damid_actdist_exp of
+ * igm/steps/NuclDamidActivationDistanceStep.py:476-570, whose snormsq_exp (:78-110)
+ * measures voxel to voxel inside the grid, |(voxel - edt(voxel)) * grid|^2; the
+ * out-of-grid branch, the sort, pnow and the rows are those of shape 2. */
 #define IGM_DAMID_SPHERE 0
 #define IGM_DAMID_ELLIPSOID 1
 #define IGM_DAMID_EXP_MAP 2
+#define IGM_DAMID_EXP_MAP_NUCL 3
 
 typedef struct {
     int32_t loc; /* diploid bead index                               */
@@ -245,6 +250,30 @@ typedef struct {
  * NULL = map 0 for every structure.  nmap = 0 clears. */
 int igm_mstep_set_volumes(igm_ctx* ctx, int32_t nmap, const igm_volume_map* maps,
                           const int32_t* struct_map, int32_t nstruct);
+
+/* One table per envelope: env_map[s] is the index into the staged maps that envelope
+ * `env` (0 <= env < IGM_MAX_ENVELOPES) reads for structure s of the next igm_mstep_*
+ * calls, so a nucleolus body can sit beside the nucleus map.  NULL restores the default
+ * table (struct_map above); igm_mstep_set_volumes clears every per-envelope table.
+ * Host pointer; indices are checked against the staged maps, nstruct against the batch
+ * size of the calls that follow. */
+int igm_mstep_set_envelope_maps(igm_ctx* ctx, int32_t env, const int32_t* env_map, int32_t nstruct);
+
+/* Volumetric lamina membership (M-step restraint assembly): GenDamid._apply_envelope
+ * (igm/restraints/gendamid.py:17-47,101-107) for every structure at once, on the maps
+ * staged by igm_mstep_set_volumes.  out_flags[s, a] = base | (env_bit if some row
+ * {loc = a, dist = d} has snormsq_exp(x_sa, map struct_map[s]) < d**2), bit-exact with
+ * the reference's NumPy 1.x arithmetic (d**2 is float64(d)^2).  struct_map[s] is
+ * the index into the staged maps (NULL: the default table of igm_mstep_set_volumes).
+ * base_flags is (natom), or (nstruct, natom) when base_per_struct != 0 -- the output of
+ * an earlier selection, so the lamina and the nuclear-body selections compose on one
+ * array.  Rows whose loc is outside [0, natom) are ignored; nrows = 0 is valid.
+ * n_selected (nullable): rows selected per structure.  The result feeds igm_mstep_run
+ * with IGM_MSTEP_STRUCT_FLAGS and a volume envelope whose k is -contact_kspring. */
+int igm_volume_select(igm_ctx* ctx, uint32_t flags, int32_t nstruct, int32_t natom, const float* xyz,
+                      const igm_damid_row* rows, int64_t nrows, const int32_t* struct_map,
+                      uint32_t env_bit, const uint32_t* base_flags, int32_t base_per_struct,
+                      uint32_t* out_flags, int32_t* n_selected);
 
 /* ---- M-step ---------------------------------------------------------------
  * Batched replacement of lammps.optimize (lammps.py:361-492): the protocol of
