@@ -47,6 +47,9 @@ optinfo_dtype = np.dtype([('final_energy', '<f8'), ('pair_energy', '<f8'), ('bon
                           ('cg_iters', '<i4'), ('cg_evals', '<i4'), ('stop_reason', '<i4'), ('nrebuild', '<i4')])
 assert pair_dtype.itemsize == 24 and row_dtype.itemsize == 16 and result_dtype.itemsize == 32
 assert bond_dtype.itemsize == 16
+# igm_anchor: a harmonic upper bound between an atom and a fixed point (chromatin tracing)
+anchor_dtype = np.dtype([('atom', '<u4'), ('x', '<f4'), ('y', '<f4'), ('z', '<f4'), ('r0', '<f4'), ('k', '<f4')])
+assert anchor_dtype.itemsize == 24
 
 LOWER_BOUND_BIT = np.uint32(1 << 31)
 
@@ -137,6 +140,8 @@ SIGNATURES = {
     'igm_volume_select': (_i32, [_vp, _u32, _i32, _i32, _vp, _vp, _i64, _vp, _u32, _vp, _i32, _vp, _vp]),
     'igm_mstep_violations': (_i32, [_vp, _u32, ctypes.POINTER(MStepParams), _i32, _i32, _vp, _vp, _vp,
                                     _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _f64, _vp]),
+    'igm_mstep_set_anchors': (_i32, [_vp, _i32, _vp, _vp]),
+    'igm_mstep_anchor_violations': (_i32, [_vp, _u32, _i32, _i32, _vp, _f64, _vp]),
 }
 
 _lib = None

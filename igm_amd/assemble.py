@@ -21,6 +21,9 @@ as the flat arrays the batched engine consumes.
                                                         (igm_volume_select)
   Sprite            sprite.py:36-71 (:456-480)          centroid slots + per-structure bonds
   Fish              fish.py:85-266 (:482-503)           per-structure bonds to the centre
+  Tracing           tracing.py:36-61 (:281-300)         position anchors (igm_anchor): the
+                                                        reference's static centroids without
+                                                        the centroid atoms
 
 Atom layout shared by the batch: the beads, ONE static centre dummy at the origin
 (the Envelope/Damid/Fish centres are the same frozen point; LammpsModel merges the
@@ -30,7 +33,8 @@ this module does not implement raises -- nothing in the config is dropped silent
 
 Violation classes (the kernel's record index -> the reference's vstat key,
 repr(restraint), in ModelingStep's monitored_restraints order): bond classes
-POLYMER, INTER_HIC, INTRA_HIC, SPRITE, FISH, then one class per envelope.
+POLYMER, INTER_HIC, INTRA_HIC, SPRITE, FISH, then one class per envelope; with a
+tracing spec, and only then, one trailing class 'Tracing' (the anchor record).
 """
 import numpy as np
 
@@ -114,7 +118,8 @@ def build(xyz, sids, index, spec, ctx, select=None):
                 (exp_map envelope only),
       nucldamid {rows, contact_range, k} or None (needs nucleolus),
       sprite    {assignment, indptr, selected, volume_fraction, k} or None,
-      fish      {data (fish_assignment dict), rtype, tol, k} or None.
+      fish      {data (fish_assignment dict), rtype, tol, k} or None,
+      tracing   {data (tracing.read_assignment dict), tol, k} or None.
     ctx: the igm context of the device; select: the selection backend (default
     DeviceSelect(ctx); the CPU tests pass the oracle's)."""
     from . import restraints as R
@@ -265,18 +270,32 @@ def build(xyz, sids, index, spec, ctx, select=None):
                                     for p, c in parts]).astype(np.int32))
     ptr, bonds = M.concat_bonds(per)
     bcls = np.concatenate(pcls) if pcls else np.zeros(0, np.int32)
+    # ---- tracing: position anchors, recorded as one trailing class
+    tr = spec.get('tracing')
+    anchor_ptr = anchors = None
+    tr_names = []
+    if tr is not None:
+        from . import tracing as T
+        anchor_ptr, anchors = T.anchors_for(tr['data'], sids, float(tr['tol']), float(tr['k']), nbead=nbead)
+        tr_names = ['Tracing']
     return Batch(x=x, radii=radii, flags=flags, prm=prm, poly=poly,
                  poly_cls=np.full(len(poly), M.CLASS_POLYMER, np.int32), ptr=ptr, bonds=bonds, bcls=bcls,
-                 class_cr=class_cr, env_scale=np.asarray(env_scale, np.float64), names=names + env_names,
-                 nbead=nbead, natom=natom, nslot=nslot, active=active, centre=centre, volumes=volumes)
+                 class_cr=class_cr, env_scale=np.asarray(env_scale, np.float64), names=names + env_names + tr_names,
+                 nbead=nbead, natom=natom, nslot=nslot, active=active, centre=centre, volumes=volumes,
+                 anchor_ptr=anchor_ptr, anchors=anchors)
 
 
 def run(batch, seeds, tol, ctx):
     """model.optimize + the violation records of a Batch: (x (S, natom, 3), info,
-    stats (S, ncls, 104))."""
+    stats (S, ncls, 104)); a batch with tracing anchors runs with them and carries their
+    record as the last class."""
     from . import mstep
+    anchors = (batch.anchor_ptr, batch.anchors) if getattr(batch, 'anchors', None) is not None else None
     xo, info = mstep.run(batch.prm, batch.x, batch.radii, batch.flags, batch.poly, batch.ptr, batch.bonds, seeds,
-                         ctx=ctx)
+                         ctx=ctx, anchors=anchors)
     stats = mstep.violations(batch.prm, xo, batch.radii, batch.flags, batch.poly, batch.poly_cls, batch.ptr,
                              batch.bonds, batch.bcls, batch.class_cr, batch.env_scale, float(tol), ctx=ctx)
+    if anchors is not None:
+        rec = mstep.anchor_violations(xo, float(tol), anchors, ctx=ctx)
+        stats = np.concatenate([stats, rec[:, None, :]], axis=1)
     return xo, info, stats

@@ -1,4 +1,6 @@
 // Context management of libigmhip.so (include/igm_hip.h).
+#include <cmath>
+
 #include "igm_ctx.h"
 
 extern "C" {
@@ -60,6 +62,37 @@ int igm_ctx_set_stream(igm_ctx* c, void* s) {
 int igm_ctx_synchronize(igm_ctx* c) {
     if (!c) return IGM_E_INVALID;
     IGM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    return IGM_OK;
+}
+
+// Position anchors of the igm_mstep_* calls that follow: validated and kept on the host;
+// every call builds the device form for its own batch (mstep.hip: stage_anchors).
+int igm_mstep_set_anchors(igm_ctx* c, int32_t nstruct, const int64_t* anchor_ptr, const igm_anchor* anchors) {
+    using igm::fail;
+    if (!c) return IGM_E_INVALID;
+    if (nstruct < 0 || (nstruct > 0 && !anchor_ptr))
+        return fail(c, IGM_E_INVALID, "igm_mstep_set_anchors: invalid arguments");
+    c->anch_ptr_h.clear();
+    c->anch_h.clear();
+    if (nstruct == 0) return IGM_OK;
+    if (anchor_ptr[0] != 0) return fail(c, IGM_E_INVALID, "igm_mstep_set_anchors: anchor_ptr[0] = %lld, not 0",
+                                        (long long)anchor_ptr[0]);
+    for (int s = 0; s < nstruct; ++s)
+        if (anchor_ptr[s + 1] < anchor_ptr[s])
+            return fail(c, IGM_E_INVALID, "igm_mstep_set_anchors: anchor_ptr is not monotone at structure %d", s);
+    const int64_t n = anchor_ptr[nstruct];
+    if (n > 0 && !anchors) return fail(c, IGM_E_INVALID, "igm_mstep_set_anchors: anchors is NULL");
+    if (n + nstruct > 0x7fffffff) return fail(c, IGM_E_UNSUPPORTED, "igm_mstep_set_anchors: %lld anchors", (long long)n);
+    for (int64_t q = 0; q < n; ++q) {
+        const igm_anchor& a = anchors[q];
+        if (!std::isfinite(a.x) || !std::isfinite(a.y) || !std::isfinite(a.z))
+            return fail(c, IGM_E_INVALID, "igm_mstep_set_anchors: anchor %lld has a non-finite target", (long long)q);
+        if (!std::isfinite(a.r0) || !std::isfinite(a.k))
+            return fail(c, IGM_E_INVALID, "igm_mstep_set_anchors: anchor %lld has a non-finite r0 or k", (long long)q);
+        if (a.r0 < 0.0f) return fail(c, IGM_E_INVALID, "igm_mstep_set_anchors: anchor %lld has r0 < 0", (long long)q);
+    }
+    c->anch_ptr_h.assign(anchor_ptr, anchor_ptr + nstruct + 1);
+    c->anch_h.assign(anchors, anchors + n);
     return IGM_OK;
 }
 

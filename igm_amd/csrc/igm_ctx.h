@@ -27,6 +27,10 @@ struct igm_ctx {
     // igm_mstep_set_envelope_maps (empty: envelope e reads the default table)
     std::vector<int> vol_smap_h;
     std::vector<int> vol_emap_h[IGM_MAX_ENVELOPES];
+    // position anchors staged by igm_mstep_set_anchors (host copies; the igm_mstep_* calls
+    // build their device form, ws slots "ms_anch" / "ms_aidx" / "ms_nanch")
+    std::vector<int64_t> anch_ptr_h;  // (nstruct + 1), empty: nothing staged
+    std::vector<igm_anchor> anch_h;
     int num_cus = 256;
     // last HBM-size anneal: {K, slots, builds, re-cuts, largest resident set, largest
     // owned set, abort (0: the domain-decomposed engine ran; -1 / > 0: the population
@@ -184,6 +188,63 @@ inline int envelope_map_tables(igm_ctx* c, int nstruct, const int** table, int* 
     IGM_HIP_CHECK(c, hipStreamSynchronize(c->stream));  // tab dies here
     *table = (const int*)ps;
     *stride = nstruct;
+    return IGM_OK;
+}
+
+// Device form of the anchors staged by igm_mstep_set_anchors for a call over nstruct
+// structures of natom atoms (all NULL: nothing staged, the kernels without the term run):
+//   anch   every structure's anchors sorted by atom -- a stable sort, so the anchors of one
+//          atom keep the order given -- each structure closed by a sentinel (atom = ~0u)
+//   aidx   (nstruct, natom): index in anch of the atom's first anchor, -1 = none; an atom's
+//          anchors are the entries from there on that carry its id
+//   nanch  (nstruct) anchors of the structure (thermo temp of group all)
+struct AnchorsDev {
+    const igm_anchor* anch;
+    const int* aidx;
+    const int* nanch;
+};
+
+inline int stage_anchors(igm_ctx* c, int nstruct, int natom, AnchorsDev* out) {
+    *out = AnchorsDev{nullptr, nullptr, nullptr};
+    if (c->anch_ptr_h.empty()) return IGM_OK;
+    if ((int)c->anch_ptr_h.size() != nstruct + 1)
+        return fail(c, IGM_E_INVALID, "anchors staged for %d structures, batch has %d (igm_mstep_set_anchors)",
+                    (int)c->anch_ptr_h.size() - 1, nstruct);
+    const int64_t n = c->anch_ptr_h[nstruct];
+    if (n == 0) return IGM_OK;  // every row empty: the code path of nothing staged
+    std::vector<igm_anchor> dev((size_t)n + nstruct);
+    std::vector<int> idx((size_t)nstruct * natom, -1), cnt(nstruct);
+    std::vector<int> first(natom + 1);
+    for (int s = 0; s < nstruct; ++s) {
+        const int64_t b0 = c->anch_ptr_h[s], b1 = c->anch_ptr_h[s + 1];
+        const igm_anchor* src = c->anch_h.data() + b0;
+        const int m = (int)(b1 - b0);
+        cnt[s] = m;
+        std::fill(first.begin(), first.end(), 0);
+        for (int q = 0; q < m; ++q) {
+            if (src[q].atom >= (uint32_t)natom)
+                return fail(c, IGM_E_INVALID, "anchor %d of structure %d: atom %u >= natom %d", q, s, src[q].atom,
+                            natom);
+            ++first[src[q].atom + 1];
+        }
+        const size_t base = (size_t)b0 + s;  // one sentinel per earlier structure
+        int* ix = idx.data() + (size_t)s * natom;
+        for (int a = 0; a < natom; ++a) {
+            if (first[a + 1] > 0) ix[a] = (int)(base + first[a]);
+            first[a + 1] += first[a];
+        }
+        for (int q = 0; q < m; ++q) dev[base + first[src[q].atom]++] = src[q];  // counting sort: stable
+        dev[base + m] = igm_anchor{~0u, 0.f, 0.f, 0.f, 0.f, 0.f};
+    }
+    void *pa, *pi, *pn;
+    IGM_TRY(workspace(c, "ms_anch", sizeof(igm_anchor) * dev.size(), &pa));
+    IGM_TRY(workspace(c, "ms_aidx", sizeof(int) * idx.size(), &pi));
+    IGM_TRY(workspace(c, "ms_nanch", sizeof(int) * cnt.size(), &pn));
+    IGM_HIP_CHECK(c, hipMemcpyAsync(pa, dev.data(), sizeof(igm_anchor) * dev.size(), hipMemcpyHostToDevice, c->stream));
+    IGM_HIP_CHECK(c, hipMemcpyAsync(pi, idx.data(), sizeof(int) * idx.size(), hipMemcpyHostToDevice, c->stream));
+    IGM_HIP_CHECK(c, hipMemcpyAsync(pn, cnt.data(), sizeof(int) * cnt.size(), hipMemcpyHostToDevice, c->stream));
+    IGM_HIP_CHECK(c, hipStreamSynchronize(c->stream));  // the host vectors die here
+    *out = AnchorsDev{(const igm_anchor*)pa, (const int*)pi, (const int*)pn};
     return IGM_OK;
 }
 

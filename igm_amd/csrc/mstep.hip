@@ -826,11 +826,13 @@ __device__ __forceinline__ void env_terms(int s, T xi, T yi, T zi, T ri, uint32_
 // Total force on atom a, gathered by its owner thread: pairs from the Verlet
 // list (or the cell walk around the build-time position b*), bonds B, envelopes
 // (the CG kernel; the f32 MD kernel uses atom_force_md).
-template <typename T, bool EN, typename OffT, int PB = IGM_PAIR_BATCH>
+// AN: the position anchors of igm_mstep_set_anchors (compiled in only for runs that stage them).
+template <typename T, bool EN, typename OffT, bool AN = false, int PB = IGM_PAIR_BATCH>
 __device__ __forceinline__ void atom_force(int s, int a, const vec4_t<T>& p0, uint32_t fl, const vec4_t<T>* pos,
                                            const NList<T, OffT>& L, T bx, T by, T bz, const BondView& B,
                                            const DevParams& P, T evf, T envf, T& fx, T& fy,
-                                           T& fz, double& ep, double& eb, double (&ee)[IGM_MAX_ENVELOPES]) {
+                                           T& fz, double& ep, double& eb, double (&ee)[IGM_MAX_ENVELOPES],
+                                           const AnchorsDev An = AnchorsDev{nullptr, nullptr, nullptr}) {
     fx = fy = fz = T(0);
     const T xi = p0.x, yi = p0.y, zi = p0.z;
     const T ri = (T)p0.w;
@@ -856,6 +858,7 @@ __device__ __forceinline__ void atom_force(int s, int a, const vec4_t<T>& p0, ui
         }
     }
     hbm_bonds<T, EN>(xi, yi, zi, pos, B, fx, fy, fz, eb);
+    if constexpr (AN) anchor_terms<T, EN>(An, P.natom, s, a, xi, yi, zi, fx, fy, fz, eb);
     env_terms<T, EN>(s, xi, yi, zi, ri, fl, P, envf, fx, fy, fz, ee);
 }
 
@@ -901,12 +904,13 @@ __device__ __forceinline__ uint32_t bond_candidates(const float4& p, const uint1
 // the filter pass is a gather, 6 FMA-class ops and a compare.  Entries are
 // visited in slot order in both passes (fixed summation order).  LDS bonds take
 // one rsq each from the type table {r0^2, 2 k r0, -2 k}: f/r = 2 k r0/r - 2 k.
-template <int U>
+template <int U, bool AN = false>
 __device__ __forceinline__ void atom_force_md(int s, int a, const float4& p0, uint32_t fl, const float4* pos,
                                               const NList<float, uint16_t>& L, float bx, float by, float bz,
                                               const BondView& B, const DevParams& P, float evf,
                                               float envf, float& fx, float& fy, float& fz, int amax,
-                                              uint32_t bmask = 0xffffffffu) {
+                                              uint32_t bmask = 0xffffffffu,
+                                              const AnchorsDev An = AnchorsDev{nullptr, nullptr, nullptr}) {
     fx = fy = fz = 0.0f;
     const float xi = p0.x, yi = p0.y, zi = p0.z, ri = p0.w;
     double unused = 0.0;
@@ -1020,6 +1024,7 @@ __device__ __forceinline__ void atom_force_md(int s, int a, const float4& p0, ui
     } else {
         hbm_bonds<float, false>(xi, yi, zi, pos, B, fx, fy, fz, unused);
     }
+    if constexpr (AN) anchor_terms_md(An, P.natom, s, a, xi, yi, zi, fx, fy, fz);
     double ee[IGM_MAX_ENVELOPES];
     env_terms<float, false>(s, xi, yi, zi, ri, fl, P, envf, fx, fy, fz, ee);
 }
@@ -1110,8 +1115,13 @@ __device__ __forceinline__ float pick(const float (&arr)[BPT][3], int b, int d) 
     return r;
 }
 
-template <int NT, int BPT>
-__global__ void __launch_bounds__(NT) anneal_kernel(AnnealArgs A) {
+// the arguments of the instantiations with the anchor term
+struct AnnealArgsAn : AnnealArgs {
+    AnchorsDev an;
+};
+
+template <int NT, int BPT, bool AN = false>
+__global__ void __launch_bounds__(NT) anneal_kernel(std::conditional_t<AN, AnnealArgsAn, AnnealArgs> A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int npad = NT * BPT;
     MdLds sm = carve_md_lds(smem, npad);
@@ -1257,10 +1267,10 @@ __global__ void __launch_bounds__(NT) anneal_kernel(AnnealArgs A) {
                                                      : BondView{adj + soff[a >> 6] + lane, bt, nullptr, nullptr, deg[a]};
                         const uint32_t f5 = (flk >> (5 * b)) & 31u;
                         const uint32_t fla = ((f5 & 1u) ? IGM_ATOM_FIXED : 0u) | ((f5 >> 1) << 4);
-                        atom_force_md<kLdsPairBatch>(s, a, sm.pos[a], fla, sm.pos,
+                        atom_force_md<kLdsPairBatch, AN>(s, a, sm.pos[a], fla, sm.pos,
                                                      sm.L, pick<BPT>(xb, b, 0), pick<BPT>(xb, b, 1),
                                                      pick<BPT>(xb, b, 2), B, A.P, evf, envf, fx, fy, fz,
-                                                     natom - 1, pick<BPT>(bmk, b));
+                                                     natom - 1, pick<BPT>(bmk, b), anchors_of<AN>(A));
 #pragma unroll
                         for (int i = 0; i < BPT; ++i) {  // (unconditional selects: no store to a selected address)
                             f[i][0] = b == i ? fx : f[i][0];
@@ -2505,10 +2515,14 @@ __device__ __noinline__ float4 pop_walk_pairs(const float4* pos, const int* cell
 // (nn_built entries) and is read from there; the slot's bonds are re-indexed from the
 // atom-space adjacency into the new slot order here (written to bent/bdeg for the
 // following steps) and used directly.
+//   AN: the position anchors of the slot's ATOM (aid of the slot: anchors belong to atom
+// ids, whatever the slot order), added after the bonds.
+template <bool AN>
 __device__ __forceinline__ void pop_slot_force(const PopArgs& A, int s, int i, size_t base, const float4* pos,
                                                uint32_t fl, float evf, float envf, float& fx, float& fy,
                                                float& fz, const IGM_LDS float2* sbt, bool lds_types,
-                                               const uint32_t* lrow = nullptr, int nn_built = 0) {
+                                               const AnchorsDev An, const uint32_t* lrow = nullptr,
+                                               int nn_built = 0) {
     constexpr int U = kPopPairBatch;  // list quads per batch
     const int nsl = A.cm.nslice;
     const uint2* gl = A.nl + ((size_t)s * nsl + (i >> 6)) * A.kq * 64 + (i & 63);
@@ -2682,6 +2696,7 @@ __device__ __forceinline__ void pop_slot_force(const PopArgs& A, int s, int i, s
     fx += bfx;
     fy += bfy;
     fz += bfz;
+    if constexpr (AN) anchor_terms_md(An, A.cm.natom, s, A.buf[A.par[s]].aid[base + i], xi, yi, zi, fx, fy, fz);
     // envelopes (non-bead atoms carry -(radius + 1))
     const float rad = ri >= 0.0f ? ri : -ri - 1.0f;
     for (int e = 0; e < A.P.nenv; ++e) {
@@ -2726,8 +2741,13 @@ __device__ __forceinline__ void pop_slot_force(const PopArgs& A, int s, int i, s
 //   (Block windows staged in LDS, every neighbour inside them an LDS read instead of a
 // gather: round 5 with window-form lists, round 6 with the slot -> window mapping in this
 // kernel -- both slower on config C, profiles/r05_ab and profiles/r06_ab.)
-template <bool FUSED>
-__global__ void __launch_bounds__(kPopBS, IGM_POP_FORCE_OCC) pop_force_kernel(PopArgs A, float evf, float envf, PopStep S) {
+struct PopArgsAn : PopArgs {
+    AnchorsDev an;  // (aidx offset to the view's first structure, as the per-structure arrays)
+};
+
+template <bool FUSED, bool AN = false>
+__global__ void __launch_bounds__(kPopBS, IGM_POP_FORCE_OCC) pop_force_kernel(std::conditional_t<AN, PopArgsAn, PopArgs> A,
+                                                                              float evf, float envf, PopStep S) {
     __shared__ double red[kPopBS / 64];
     __shared__ uint32_t lrow[FUSED ? kPopBS * kPopListRow / 2 : 1];
     const int lb = pop_block(), s = lb / A.nbs, blk = lb % A.nbs, i = blk * kPopBS + threadIdx.x;
@@ -2771,9 +2791,9 @@ __global__ void __launch_bounds__(kPopBS, IGM_POP_FORCE_OCC) pop_force_kernel(Po
                                           kPopListRow - 2);
             else
                 A.nnb[k] = 0;
-            pop_slot_force(A, s, i, base, B.pos + base, fl, evf, envf, fx, fy, fz, (const IGM_LDS float2*)sbt, lds_types, row, nb);
+            pop_slot_force<AN>(A, s, i, base, B.pos + base, fl, evf, envf, fx, fy, fz, (const IGM_LDS float2*)sbt, lds_types, anchors_of<AN>(A), row, nb);
         } else {
-            pop_slot_force(A, s, i, base, B.pos + base, fl, evf, envf, fx, fy, fz, (const IGM_LDS float2*)sbt, lds_types);
+            pop_slot_force<AN>(A, s, i, base, B.pos + base, fl, evf, envf, fx, fy, fz, (const IGM_LDS float2*)sbt, lds_types, anchors_of<AN>(A));
         }
         B.frc[k] = pop_f3{fx, fy, fz};
         if (S.integrate && !(fl & IGM_ATOM_FIXED)) {
@@ -3024,8 +3044,12 @@ __host__ __device__ inline size_t carve_cg_lds(void* smem, int npad, bool big, C
     return cv.o;
 }
 
-template <int NT, bool BIG>
-__global__ void __launch_bounds__(NT) cg_kernel(CGArgs A) {
+struct CGArgsAn : CGArgs {
+    AnchorsDev an;
+};
+
+template <int NT, bool BIG, bool AN = false>
+__global__ void __launch_bounds__(NT) cg_kernel(std::conditional_t<AN, CGArgsAn, CGArgs> A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int t = threadIdx.x, lane = t & 63;
     const int natom = A.cm.natom, ldn = A.cm.ldn;
@@ -3111,8 +3135,9 @@ __global__ void __launch_bounds__(NT) cg_kernel(CGArgs A) {
                 double e_e[IGM_MAX_ENVELOPES] = {0, 0, 0, 0};
                 double fx, fy, fz;
                 const BondView B{adj + soff[a >> 6] + lane, bt, nullptr, nullptr, deg[a]};
-                atom_force<double, true, int>(s, a, pos[a], A.cm.aflags[(size_t)s * A.cm.afs + a], pos, L, XB[a], XB[ldn + a],
-                                              XB[2 * ldn + a], B, A.P, A.evf, A.envf, fx, fy, fz, vv[0], vv[1], e_e);
+                atom_force<double, true, int, AN>(s, a, pos[a], A.cm.aflags[(size_t)s * A.cm.afs + a], pos, L, XB[a], XB[ldn + a],
+                                              XB[2 * ldn + a], B, A.P, A.evf, A.envf, fx, fy, fz, vv[0], vv[1], e_e,
+                                                   anchors_of<AN>(A));
                 for (int e = 0; e < IGM_MAX_ENVELOPES; ++e) vv[2 + e] += e_e[e];
                 F[a] = fx;
                 F[ldn + a] = fy;
@@ -3304,7 +3329,11 @@ __global__ void __launch_bounds__(NT) cg_kernel(CGArgs A) {
                 I.pair_energy = ep;
                 I.bond_energy = eb;
                 for (int e = 0; e < IGM_MAX_ENVELOPES; ++e) I.env_energy[e] = ee[e];
-                const double dof_all = 3.0 * natom - 3.0;  // thermo temp: group all
+                // thermo temp: group all; every anchor counts as the motionless centroid atom
+                // the reference would add for it (igm_hip.h: igm_anchor)
+                int nfix = 0;
+                if constexpr (AN) nfix = A.an.nanch[s];
+                const double dof_all = 3.0 * (natom + nfix) - 3.0;
                 I.temp = dof_all > 0 ? fn[1] / dof_all : 0.0;
                 I.einitial = einitial;
                 I.fnorm_final = sqrt(fn[0]);
@@ -3520,6 +3549,7 @@ struct Prepared {
     DevParams P;
     int64_t total_ent;
     bool big;  // HBM-resident kernels
+    AnchorsDev an;  // all null: no anchors, the kernels without the term
 };
 
 // The reference writes np.float32 values with Python's shortest round-trip repr
@@ -3764,6 +3794,7 @@ int prepare(igm_ctx* c, uint32_t flags, const igm_mstep_params* prm, int32_t nst
     DevParams P;
     const int* d_atype;
     IGM_TRY(make_devparams(c, prm, nstruct, natom, d_radii, d_flags, &P, &d_atype));
+    IGM_TRY(stage_anchors(c, nstruct, natom, &out->an));  // the anchors of igm_mstep_set_anchors, if any
     const int nslice = P.nslice;
     void *p_deg, *p_fill, *p_soff, *p_size, *p_base, *p_nt, *p_tb, *p_err, *p_wc;
     IGM_TRY(workspace(c, "ms_deg", sizeof(int) * (size_t)nstruct * natom, &p_deg));
@@ -3977,7 +4008,8 @@ int run_anneal_pop(igm_ctx* c, const Prepared& pr, const AnnealArgs& A) {
         // 2 x 2, slot remaps 8, pruned bonds 4 bdmax + 2; per structure the cell offsets.  At
         // config C (1000 x 29 839 slots) the lists alone are 15.3 GB.  Checked against the free
         // HBM (plus what this context's population workspace already holds) before anything
-        // is allocated.
+        // is allocated.  (Staged anchors -- 24 B each and 4 B per (structure, atom) -- were
+        // allocated by prepare(): the free HBM read here already lacks them.)
         const size_t per_slot = 2 * (16 + 12 + 12 + 4 + 4 + 1) + 12 + 8 * (size_t)Q.kq + 2 + 12 * (size_t)Q.bdmax + 6 +
                                 8 + 4;
         const size_t need = per_slot * SL + sizeof(int) * (size_t)S * (kPopCells + kPopCntStride);
@@ -4215,7 +4247,20 @@ int run_anneal_pop(igm_ctx* c, const Prepared& pr, const AnnealArgs& A) {
     // throughput, not by the groups' launch chains, so the shorter chain buys nothing and the
     // second launch and cross-stream events cost.
     const bool early = knob("IGM_POP_EARLY", 0) != 0 && !kPopFused;
-    auto force_kern = pop_force_kernel<kPopFused>;
+    // the force launch of group g: with anchors staged the instantiation with the term, whose
+    // arguments carry them (aidx offset to the group's first structure)
+    const bool anchored = pr.an.aidx != nullptr;
+    auto launch_force = [&](const PopArgs& Vg, int s0, dim3 grid, hipStream_t sg, float evf, float envf,
+                            const PopStep& ps) {
+        if (anchored) {
+            PopArgsAn VA;
+            static_cast<PopArgs&>(VA) = Vg;
+            VA.an = AnchorsDev{pr.an.anch, pr.an.aidx + (size_t)s0 * N, pr.an.nanch + s0};
+            hipLaunchKernelGGL((pop_force_kernel<kPopFused, true>), grid, dim3(kPopBS), 0, sg, VA, evf, envf, ps);
+        } else {
+            hipLaunchKernelGGL((pop_force_kernel<kPopFused>), grid, dim3(kPopBS), 0, sg, Vg, evf, envf, ps);
+        }
+    };
     IGM_TRY(aux_streams(c, nc + (early ? ng : 0)));
     std::vector<hipEvent_t> ev_int(early ? ng : 0), ev_frc(early ? ng : 0);
     for (int g = 0; g < (early ? ng : 0); ++g) {
@@ -4317,8 +4362,7 @@ int run_anneal_pop(igm_ctx* c, const Prepared& pr, const AnnealArgs& A) {
                             s1.part = 1;
                             IGM_HIP_CHECK(c, hipEventRecord(ev_int[g], sg));
                             IGM_HIP_CHECK(c, hipStreamWaitEvent(side(g), ev_int[g], 0));
-                            hipLaunchKernelGGL(force_kern, grid_of(g), blk, 0, side(g), V[g], evf,
-                                               envf, s1);
+                            launch_force(V[g], g0[g], grid_of(g), side(g), evf, envf, s1);
                             IGM_HIP_CHECK(c, hipEventRecord(ev_frc[g], side(g)));
                         }
                         if (split) {
@@ -4339,7 +4383,7 @@ int run_anneal_pop(igm_ctx* c, const Prepared& pr, const AnnealArgs& A) {
                         }
                         PopStep s2 = st;
                         s2.part = early ? 2 : 0;
-                        hipLaunchKernelGGL(force_kern, grid_of(g), blk, 0, sg, V[g], evf, envf, s2);
+                        launch_force(V[g], g0[g], grid_of(g), sg, evf, envf, s2);
                         if (early) IGM_HIP_CHECK(c, hipStreamWaitEvent(sg, ev_frc[g], 0));  // (the next integrate)
                         if (pst && step % stats_every == 0)
                             hipLaunchKernelGGL(pop_stats_kernel, grid_of(g), blk, 0, sg, V[g], pst + 16 * seg);
@@ -4394,6 +4438,32 @@ int run_anneal_pop(igm_ctx* c, const Prepared& pr, const AnnealArgs& A) {
 int run_anneal_big(igm_ctx* c, const Prepared& pr, const AnnealArgs& A, int32_t pflags) {
     if (pflags & 0x4) return fail(c, IGM_E_UNSUPPORTED, "the domain-decomposed engine (params flag 0x4) is retired");
     return run_anneal_pop(c, pr, A);
+}
+
+// the LDS anneal launch (AN: the instantiation with the anchor term and its arguments)
+template <int NT, int BPT, bool AN>
+int launch_anneal_lds(igm_ctx* c, const Prepared& pr, AnnealArgs A) {
+    const size_t lds = kLdsBytes;
+    auto kern = anneal_kernel<NT, BPT, AN>;
+    IGM_HIP_CHECK(c, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    int grid = 0;
+    IGM_TRY(resident_grid(c, kern, NT, lds, pr.cm.nstruct, &grid));
+    // + slack: the batched force loop reads up to IGM_PAIR_BATCH - 1 slots past a list
+    A.ws_stride = ((size_t)pr.cm.ldn * (pr.cm.kcap - kLdsListSlots) * 2 + 64 * 2 * IGM_PAIR_BATCH + 255) & ~size_t(255);
+    void* ws;
+    IGM_TRY(workspace(c, "ms_ldsovf", A.ws_stride * (size_t)grid, &ws));
+    A.ws = (unsigned char*)ws;
+    Timed tm(c, "anneal");
+    if constexpr (AN) {
+        AnnealArgsAn AA;
+        static_cast<AnnealArgs&>(AA) = A;
+        AA.an = pr.an;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, c->stream, AA);
+    } else {
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, c->stream, A);
+    }
+    IGM_HIP_CHECK(c, hipGetLastError());
+    return IGM_OK;
 }
 
 int run_anneal(igm_ctx* c, const Prepared& pr, const igm_mstep_params* prm, float* d_xyz, float* d_vel,
@@ -4519,22 +4589,44 @@ int run_anneal(igm_ctx* c, const Prepared& pr, const igm_mstep_params* prm, floa
     if (pr.big) return run_anneal_big(c, pr, A, prm->flags);
     LaunchCfg cfg;
     if (!lds_fits(pr.cm.natom, &cfg)) return fail(c, IGM_E_UNSUPPORTED, "no LDS configuration");
-    IGM_DISPATCH_ALL({
-        const size_t lds = kLdsBytes;
-        auto kern = anneal_kernel<NT, BPT>;
-        IGM_HIP_CHECK(c, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        int grid = 0;
-        IGM_TRY(resident_grid(c, kern, NT, lds, pr.cm.nstruct, &grid));
-        // + slack: the batched force loop reads up to IGM_PAIR_BATCH - 1 slots past a list
-        A.ws_stride = ((size_t)pr.cm.ldn * (pr.cm.kcap - kLdsListSlots) * 2 + 64 * 2 * IGM_PAIR_BATCH + 255) &
-                      ~size_t(255);
-        void* ws;
-        IGM_TRY(workspace(c, "ms_ldsovf", A.ws_stride * (size_t)grid, &ws));
-        A.ws = (unsigned char*)ws;
-        Timed tm(c, "anneal");
+    if (pr.an.aidx) {
+        IGM_DISPATCH_ALL(IGM_TRY((launch_anneal_lds<NT, BPT, true>(c, pr, A))))
+    } else {
+        IGM_DISPATCH_ALL(IGM_TRY((launch_anneal_lds<NT, BPT, false>(c, pr, A))))
+    }
+    return IGM_OK;
+}
+
+// the CG / force-evaluation launch (AN: the instantiation with the anchor term and its arguments)
+template <bool BIG, bool AN>
+int launch_cg(igm_ctx* c, const Prepared& pr, CGArgs A, int mode) {
+    constexpr int NT = 512;  // f64 force code: a 256-VGPR budget
+    CgLds cg;
+    const size_t lds = carve_cg_lds(nullptr, pr.cm.ldn, BIG, &cg);
+    auto kern = cg_kernel<NT, BIG, AN>;
+    IGM_HIP_CHECK(c, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    int grid = 0;
+    IGM_TRY(resident_grid(c, kern, NT, lds, pr.cm.nstruct, &grid));
+    NList<double, int> L;
+    BigWs<double> W;
+    A.ws_stride = carve_ws<double>(nullptr, pr.cm.natom, pr.cm.ldn, pr.cm.kcap, BIG ? kCellCapBig : kCellCap, BIG,
+                                   false, &L, &W);
+    void *ws, *vw;
+    IGM_TRY(workspace(c, "ms_cgws", A.ws_stride * (size_t)grid, &ws));
+    A.ws = (unsigned char*)ws;
+    A.vec_stride = 15 * (size_t)pr.cm.ldn;
+    IGM_TRY(workspace(c, "ms_cgvec", sizeof(double) * A.vec_stride * (size_t)grid, &vw));
+    A.vec_ws = (double*)vw;
+    Timed tm(c, mode == 0 ? "cg" : "forces");
+    if constexpr (AN) {
+        CGArgsAn AA;
+        static_cast<CGArgs&>(AA) = A;
+        AA.an = pr.an;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, c->stream, AA);
+    } else {
         hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, c->stream, A);
-        IGM_HIP_CHECK(c, hipGetLastError());
-    })
+    }
+    IGM_HIP_CHECK(c, hipGetLastError());
     return IGM_OK;
 }
 
@@ -4560,28 +4652,8 @@ int run_cg(igm_ctx* c, const Prepared& pr, const igm_mstep_params* prm, float* d
     A.forces_out = d_forces;
     A.energies_out = d_energies;
     IGM_HIP_CHECK(c, hipMemsetAsync(pr.cm.work_counter, 0, sizeof(int), c->stream));
-    constexpr int NT = 512;  // f64 force code: a 256-VGPR budget
-    const bool big = pr.big;
-    CgLds cg;
-    const size_t lds = carve_cg_lds(nullptr, pr.cm.ldn, big, &cg);
-    auto kern = big ? cg_kernel<NT, true> : cg_kernel<NT, false>;
-    IGM_HIP_CHECK(c, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int grid = 0;
-    IGM_TRY(resident_grid(c, kern, NT, lds, pr.cm.nstruct, &grid));
-    NList<double, int> L;
-    BigWs<double> W;
-    A.ws_stride = carve_ws<double>(nullptr, pr.cm.natom, pr.cm.ldn, pr.cm.kcap, big ? kCellCapBig : kCellCap, big,
-                                   false, &L, &W);
-    void *ws, *vw;
-    IGM_TRY(workspace(c, "ms_cgws", A.ws_stride * (size_t)grid, &ws));
-    A.ws = (unsigned char*)ws;
-    A.vec_stride = 15 * (size_t)pr.cm.ldn;
-    IGM_TRY(workspace(c, "ms_cgvec", sizeof(double) * A.vec_stride * (size_t)grid, &vw));
-    A.vec_ws = (double*)vw;
-    Timed tm(c, mode == 0 ? "cg" : "forces");
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, c->stream, A);
-    IGM_HIP_CHECK(c, hipGetLastError());
-    return IGM_OK;
+    if (pr.an.aidx) return pr.big ? launch_cg<true, true>(c, pr, A, mode) : launch_cg<false, true>(c, pr, A, mode);
+    return pr.big ? launch_cg<true, false>(c, pr, A, mode) : launch_cg<false, false>(c, pr, A, mode);
 }
 
 int check_error(igm_ctx* c, const Prepared& pr) {

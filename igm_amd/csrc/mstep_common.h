@@ -258,6 +258,55 @@ __device__ __forceinline__ T bond_term_bf(T r2, T r0, T k, bool lower, double& e
     return (active && r > T(0)) ? T(-2) * rk / r : T(0);
 }
 
+// Position anchors of atom a of structure s (An: the device form of igm_mstep_set_anchors,
+// AnchorsDev in igm_ctx.h): harmonic upper bounds to fixed points, the bond_harmonic form of
+// bond_term (E = k (r - r0)^2 past r0, force 0 at r = 0), evaluated in the order given.  The
+// energy is bond energy; no envelope factor scales a target.  The anchors travel in the
+// argument structs of the kernel instantiations compiled with the term (AN) only: the
+// kernels of a run without anchors keep their arguments, registers and scratch.
+template <typename T, bool EN>
+__device__ __forceinline__ void anchor_terms(const AnchorsDev& An, int natom, int s, int a, T xi, T yi, T zi,
+                                             T& fx, T& fy, T& fz, double& eb) {
+    int q = An.aidx[(size_t)s * natom + a];
+    if (q < 0) return;
+    for (igm_anchor an = An.anch[q]; an.atom == (uint32_t)a; an = An.anch[++q]) {
+        const T dx = xi - (T)an.x, dy = yi - (T)an.y, dz = zi - (T)an.z;
+        double e = 0.0;
+        const T fb = bond_term<T, EN>(dx * dx + dy * dy + dz * dz, (T)an.r0, (T)an.k, false, e);
+        fx += fb * dx;
+        fy += fb * dy;
+        fz += fb * dz;
+        if (EN) eb += e;
+    }
+}
+
+// the same for the f32 MD kernels: hardware rsq, branch-free (the form of the population
+// engine's bonds)
+__device__ __forceinline__ void anchor_terms_md(const AnchorsDev& An, int natom, int s, int a, float xi, float yi,
+                                                float zi, float& fx, float& fy, float& fz) {
+    int q = An.aidx[(size_t)s * natom + a];
+    if (q < 0) return;
+    for (igm_anchor an = An.anch[q]; an.atom == (uint32_t)a; an = An.anch[++q]) {
+        const float dx = xi - an.x, dy = yi - an.y, dz = zi - an.z;
+        const float r2 = dx * dx + dy * dy + dz * dz;
+        const float rinv = __builtin_amdgcn_rsqf(fmaxf(r2, 1.0e-30f));
+        const float dr = r2 * rinv - an.r0;
+        const float m = (dr > 0.0f && r2 > 0.0f) ? -2.0f * an.k * dr * rinv : 0.0f;
+        fx += m * dx;
+        fy += m * dy;
+        fz += m * dz;
+    }
+}
+
+// the anchors of a kernel's arguments (AN: the argument struct has them; else none)
+template <bool AN, typename ArgsT>
+__device__ __forceinline__ AnchorsDev anchors_of(const ArgsT& A) {
+    if constexpr (AN)
+        return A.an;
+    else
+        return AnchorsDev{nullptr, nullptr, nullptr};
+}
+
 // ellipsoidal envelope on one atom; adds force, returns energy (if EN)
 template <typename T, bool EN>
 __device__ __forceinline__ void envelope_term(T x, T y, T z, T rad, T a, T b, T c, T k, T& fx, T& fy, T& fz,

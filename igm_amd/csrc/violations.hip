@@ -160,7 +160,67 @@ __global__ void __launch_bounds__(256) violations_kernel(VArgs A) {
     for (int k = t; k < ncls * kRec; k += 256) A.stats[(size_t)s * ncls * kRec + k] = h[k];
 }
 
+// The record of the position anchors (Tracing: HarmonicUpperBound(centroid, locus, r0, k),
+// forces.py:131-139), one class per structure: the arithmetic of the bond branch above
+// with d = r0 and the f32 target in the centroid's place.
+__global__ void __launch_bounds__(256) anchor_violations_kernel(int natom, const float* xyz, const int64_t* aptr,
+                                                                const igm_anchor* anch, double tol, int64_t* stats) {
+    __shared__ int h[kRec];
+    const int s = blockIdx.x, t = threadIdx.x;
+    for (int k = t; k < kRec; k += 256) h[k] = 0;
+    __syncthreads();
+    const float* x = xyz + (size_t)s * natom * 3;
+    for (int64_t q = aptr[s] + t; q < aptr[s + 1]; q += 256) {
+        const igm_anchor an = anch[q];
+        const float p[3] = {an.x, an.y, an.z};
+        const double dist = (double)norm_f32(p, x + 3 * (size_t)an.atom);
+        const double d = (double)an.r0, k = (double)an.k;
+        double ratio = 0.0;
+        if (d != 0.0) {
+            const double score = (dist <= d) ? 0.0 : k * (dist - d);
+            ratio = score / (k * d);
+        }
+        record(h, ratio, tol);
+    }
+    __syncthreads();
+    for (int k = t; k < kRec; k += 256) stats[(size_t)s * kRec + k] = h[k];
+}
+
 }  // namespace
+
+extern "C" int igm_mstep_anchor_violations(igm_ctx* c, uint32_t flags, int32_t nstruct, int32_t natom,
+                                           const float* xyz, double tol, int64_t* stats) {
+    using namespace igm;
+    if (!c || nstruct <= 0 || natom <= 0 || !xyz || !stats)
+        return fail(c, IGM_E_INVALID, "igm_mstep_anchor_violations: invalid arguments");
+    if ((int)c->anch_ptr_h.size() != nstruct + 1)
+        return fail(c, IGM_E_INVALID, "anchors staged for %d structures, batch has %d (igm_mstep_set_anchors)",
+                    (int)c->anch_ptr_h.size() - 1, nstruct);
+    for (size_t q = 0; q < c->anch_h.size(); ++q)
+        if (c->anch_h[q].atom >= (uint32_t)natom)
+            return fail(c, IGM_E_INVALID, "anchor %zu: atom %u >= natom %d", q, c->anch_h[q].atom, natom);
+    IGM_HIP_CHECK(c, hipSetDevice(c->device));
+    const float* d_xyz;
+    IGM_TRY(to_device(c, flags, "vi_xyz", xyz, (size_t)nstruct * natom * 3, &d_xyz));
+    void *pp, *pa;
+    const size_t na = c->anch_h.size();
+    IGM_TRY(workspace(c, "vi_aptr", sizeof(int64_t) * ((size_t)nstruct + 1), &pp));
+    IGM_TRY(workspace(c, "vi_anch", sizeof(igm_anchor) * (na > 0 ? na : 1), &pa));
+    IGM_HIP_CHECK(c, hipMemcpyAsync(pp, c->anch_ptr_h.data(), sizeof(int64_t) * ((size_t)nstruct + 1),
+                                    hipMemcpyHostToDevice, c->stream));
+    if (na > 0)
+        IGM_HIP_CHECK(c, hipMemcpyAsync(pa, c->anch_h.data(), sizeof(igm_anchor) * na, hipMemcpyHostToDevice, c->stream));
+    int64_t* d_stats;
+    IGM_TRY(out_device(c, flags, "vi_stats", stats, (size_t)nstruct * kRec, &d_stats));
+    {
+        Timed tm(c, "violations");
+        hipLaunchKernelGGL(anchor_violations_kernel, dim3(nstruct), dim3(256), 0, c->stream, natom, d_xyz,
+                           (const int64_t*)pp, (const igm_anchor*)pa, tol, d_stats);
+        IGM_HIP_CHECK(c, hipGetLastError());
+    }
+    IGM_TRY(to_host(c, flags, stats, (const int64_t*)d_stats, (size_t)nstruct * kRec));
+    return finish(c, flags);
+}
 
 extern "C" int igm_mstep_violations(igm_ctx* c, uint32_t flags, const igm_mstep_params* prm, int32_t nstruct,
                                     int32_t natom, const float* xyz, const float* radii, const uint32_t* atom_flags,

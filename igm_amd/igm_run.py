@@ -15,8 +15,10 @@ up with an acceptable violation score, or max_iterations unsuccessful iterations
 
 The nucleolus exclusion body (model/restraints/nucleolus) needs no A-step; it and
 nuclDamID are modelled on an exp_map nucleus only (ModelingStep raises otherwise, as
-the reference fails there).  The unsupported section (tracing: the reference has no
-A-step for it) raises where the reference would run it.  Preprocess (genome/index,
+the reference fails there).  Chromatin tracing (restraints/tracing) has no A-step either:
+its assignment file is an input, and the loop only works through restraints/tracing/tol_list
+as it does through the FISH one (bin/igm-run:122-133, 218-223, 283-285).  A tracing section
+without assignment_file raises: the reference has no step that could produce the file.  Preprocess (genome/index,
 .hss allocation) is the caller's: the population file must exist.  No email
 notifications, no control socket.
 """
@@ -46,8 +48,8 @@ def startup_steps(cfg):
 def iteration_steps(cfg):
     """bin/igm-run:105-161"""
     R = cfg.get('restraints', {})
-    if 'tracing' in R:
-        raise NotImplementedError('restraints/tracing is not implemented on the hip kernel')
+    if 'tracing' in R:  # no step of its own (bin/igm-run:122-136); the file must be given
+        ST.tracing_assignment_file(cfg)
     steps = []
     if 'polymer' in R:
         steps.append(ST.PolymerAssignmentStep)
@@ -82,6 +84,13 @@ def run_pipeline(cfg, on_iteration=None):
     max_iter = ST.cget(cfg, 'optimization/max_iterations', 12)
     while True:
         rt['opt_iter'] = opt_iter
+        if 'tracing' in cfg.get('restraints', {}):  # bin/igm-run:122-133
+            ST.tracing_assignment_file(cfg)
+            tr = rt.setdefault('tracing', {})
+            if 'tol_list' not in tr:
+                tr['tol_list'] = list(cfg['restraints']['tracing']['tol_list'])
+            if 'tol' not in tr:
+                tr['tol'] = tr['tol_list'].pop(0)
         steps = iteration_steps(cfg)
         for S in steps:
             S(cfg).run()
@@ -95,7 +104,8 @@ def run_pipeline(cfg, on_iteration=None):
         nucldamid_inc = _remaining(cfg, 'nuclDamID', 'sigma_list')  # bin/igm-run:196-199
         fish_inc = _remaining(cfg, 'FISH', 'tol_list')
         sprite_inc = _remaining(cfg, 'sprite', 'volume_fraction_list')
-        all_done = not (hic_inc or damid_inc or nucldamid_inc or fish_inc or sprite_inc)
+        tracing_inc = _remaining(cfg, 'tracing', 'tol_list')  # bin/igm-run:218-223
+        all_done = not (hic_inc or damid_inc or nucldamid_inc or fish_inc or sprite_inc or tracing_inc)
         force = (opt_iter < min_iter - 1) and (opt_iter != 0)
         if ST.cget(cfg, 'optimization/force_last_iteration', False) and all_done and opt_iter == 0:
             force = True
@@ -119,6 +129,9 @@ def run_pipeline(cfg, on_iteration=None):
                 opt_iter = 0
             if sprite_inc:
                 del rt['sprite']['volume_fraction']
+                opt_iter = 0
+            if tracing_inc:  # bin/igm-run:283-285
+                del rt['tracing']['tol']
                 opt_iter = 0
             if all_done:
                 open(os.path.join(ST.cget(cfg, 'parameters/workdir', '.'), 'completed'), 'w').close()

@@ -10,6 +10,8 @@
                           steric + polymer + nucleus envelope (sphere / ellipsoid /
                           volumetric map), the optimizer protocol of the config, one
                           igm_mstep_run call instead of one LAMMPS process per structure.
+                          With restraints/tracing the traced loci are anchored to their
+                          targets at the fixed tolerance 50 (RelaxInit.py:186-207).
 """
 import numpy as np
 
@@ -43,8 +45,11 @@ def generate_territories(chrom_sizes, R=5000.0, rng=None):
     return out
 
 
+RELAX_TRACING_TOL = 50.0  # RelaxInit.py:194
+
+
 def relax_population(cfg, xyz, radii, chrom, copy, struct_ids, volumes=None, volume_struct_map=None, ctx=None,
-                     device=0):
+                     device=0, tracing=None):
     """RelaxInit.task for structures struct_ids: xyz (S, nbead, 3) -> relaxed (S, nbead, 3)
     float32 and the per-structure info.  cfg is the igm config dict (model/restraints/
     {excluded, polymer, envelope}, optimization/optimizer_options, runtime/step_no)."""
@@ -76,5 +81,10 @@ def relax_population(cfg, xyz, radii, chrom, copy, struct_ids, volumes=None, vol
     x[:, :nb] = xyz
     opt = cfg['optimization']['optimizer_options']
     seeds = M.lammps_seeds(opt.get('seed', 6535), struct_ids, cfg.get('runtime', {}).get('step_no', 1))  # lammps.py:435
-    xo, info = mstep.run(prm, x, atoms.radii, atoms.flags, poly, None, None, seeds, ctx=c)
+    anchors = None
+    if tracing is not None:  # tracing.read_assignment dict
+        from . import tracing as T
+        anchors = T.anchors_for(tracing, struct_ids, RELAX_TRACING_TOL, float(cfg['restraints']['tracing']['kspring']),
+                                nbead=nb)
+    xo, info = mstep.run(prm, x, atoms.radii, atoms.flags, poly, None, None, seeds, ctx=c, anchors=anchors)
     return xo[:, :nb], info

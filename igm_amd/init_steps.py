@@ -10,7 +10,12 @@
 The reference draws the territories from the unseeded global np.random (D9); here
 structure s draws from RandomState(model/init_seed (default 0) * 1000003 + s), so a
 restarted batch reproduces its structures, and the draw order inside a structure is
-the reference's (igm_amd.init.generate_territories).
+the reference's (igm_amd.init.generate_territories).  With restraints/tracing the traced
+loci are put at their targets and the loci between them interpolated
+(igm_amd.tracing.initial_coordinates, RandomInit.py:70-102); the model/init_noise draw, which
+the reference also takes from the unseeded global generator (D9), comes from the structure's
+own RandomState after the territories.  RelaxInit ties the traced loci to their targets with
+the fixed tolerance 50 (RelaxInit.py:186-207).
 """
 import os
 import shutil
@@ -39,9 +44,18 @@ class RandomInit(Step):
         R = float(rget(self.cfg, 'model/init_radius'))
         seed = int(cget(self.cfg, 'model/init_seed', 0))
         crd = store.coordinates('r+')
+        tr = None
+        if 'tracing' in (self.cfg.get('restraints') or {}):
+            from . import tracing
+            from .steps import tracing_data
+            tr = tracing.check_assignment(tracing_data(self.cfg), crd.shape[0])
+            noise = cget(self.cfg, 'model/init_noise', None)
         for sid in batch['sids']:
             rng = np.random.RandomState((seed * 1000003 + sid) % 2**32)  # (a valid RandomState seed for any init_seed)
-            crd[:, sid, :] = init.generate_territories(store.chrom_sizes, R, rng).astype(np.float32)
+            x = init.generate_territories(store.chrom_sizes, R, rng)
+            if tr is not None:
+                x = tracing.initial_coordinates(x, tr, sid, rng, None if noise is None else float(noise))
+            crd[:, sid, :] = x.astype(np.float32)
         crd.flush()
         del crd
 
@@ -66,6 +80,9 @@ def _hip_relax(store, sids, cfg, device):
     if rget(cfg, 'model/restraints/envelope/nucleus_shape') == 'exp_map':
         env = envelope_section(cfg, sids)
         kw = {'volumes': env['volumes'], 'volume_struct_map': env['struct_map']}
+    if 'tracing' in (cfg.get('restraints') or {}):
+        from .steps import tracing_data
+        kw['tracing'] = tracing_data(cfg)
     return init.relax_population(cfg, batch_coordinates(store, sids), store.radii, store.chrom, store.copy, sids,
                                  ctx=ctx, **kw)
 

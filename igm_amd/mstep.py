@@ -17,7 +17,9 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import IGM_DEVICE_PTRS, IGM_F32_PATH, bond_dtype, optinfo_dtype
+from contextlib import contextmanager
+
+from ._lib import IGM_DEVICE_PTRS, IGM_F32_PATH, anchor_dtype, bond_dtype, optinfo_dtype
 from . import model as M
 
 REC = 104  # counts[101], violated_restr, n_violations, n_imposed
@@ -48,11 +50,38 @@ def _bonds_args(shared, sptr, sbonds, nstruct):
     return shared, _np(sptr, np.int64), _np(sbonds, bond_dtype)
 
 
-def run(params, xyz, radii, flags, shared_bonds, sbond_ptr, sbonds, seeds, ctx=None, device=0):
+@contextmanager
+def _anchored(c, anchors, nstruct):
+    """Stage anchors = (ptr (S+1) int64, igm_anchor array) for the calls inside the block and
+    clear them afterwards, so a context never carries anchors into an unrelated call."""
+    if anchors is None:
+        yield
+        return
+    aptr = _np(anchors[0], np.int64)
+    anch = _np(anchors[1], anchor_dtype)
+    if aptr.shape != (nstruct + 1,):
+        raise ValueError('anchors: ptr has shape %r, the batch has %d structures' % (aptr.shape, nstruct))
+    if len(anch) < aptr[-1]:
+        raise ValueError('anchors: ptr ends at %d, %d anchors given' % (aptr[-1], len(anch)))
+    c.check(c.lib.igm_mstep_set_anchors(c.h, nstruct, aptr.ctypes.data, anch.ctypes.data if len(anch) else None),
+            'igm_mstep_set_anchors')
+    try:
+        yield
+    finally:
+        c.lib.igm_mstep_set_anchors(c.h, 0, None, None)
+
+
+def run(params, xyz, radii, flags, shared_bonds, sbond_ptr, sbonds, seeds, ctx=None, device=0, anchors=None):
     """Anneal + CG for every structure.  xyz (S, N, 3) float32 struct-major.
     Returns (xyz_out, info).  With torch device tensors everything stays on the GPU
-    and xyz is updated in place."""
+    and xyz is updated in place.  anchors = (ptr, igm_anchor array): position anchors
+    (host arrays), staged for this call only."""
     c = ctx or _lib.context(device)
+    with _anchored(c, anchors, int(xyz.shape[0])):
+        return _run(c, params, xyz, radii, flags, shared_bonds, sbond_ptr, sbonds, seeds)
+
+
+def _run(c, params, xyz, radii, flags, shared_bonds, sbond_ptr, sbonds, seeds):
     if _is_dev(xyz):
         import torch
         S, N = int(xyz.shape[0]), int(xyz.shape[1])
@@ -86,7 +115,8 @@ def run(params, xyz, radii, flags, shared_bonds, sbond_ptr, sbonds, seeds, ctx=N
     return xyz, info
 
 
-def forces(params, xyz, radii, flags, shared_bonds, sbond_ptr, sbonds, evf, envf, f32=False, ctx=None, device=0):
+def forces(params, xyz, radii, flags, shared_bonds, sbond_ptr, sbonds, evf, envf, f32=False, ctx=None, device=0,
+           anchors=None):
     """Forces (S, N, 3) and energies (S, 7) = {total, pair, bond, env0..3} (parity harness)."""
     c = ctx or _lib.context(device)
     xyz = _np(xyz, np.float32)
@@ -95,16 +125,17 @@ def forces(params, xyz, radii, flags, shared_bonds, sbond_ptr, sbonds, evf, envf
     f = np.zeros((S, N, 3), np.float32)
     e = np.zeros((S, 7), np.float64)
     prm = _prm(params, flags)
-    rc = c.lib.igm_mstep_forces(c.h, IGM_F32_PATH if f32 else 0, ctypes.byref(prm), S, N, xyz.ctypes.data,
-                                _np(radii, np.float32).ctypes.data, _np(flags, np.uint32).ctypes.data,
-                                shared.ctypes.data if len(shared) else None, len(shared), _lib.ptr(sptr),
-                                _lib.ptr(sb), float(evf), float(envf), f.ctypes.data, e.ctypes.data)
-    c.check(rc, 'igm_mstep_forces')
+    with _anchored(c, anchors, S):
+        rc = c.lib.igm_mstep_forces(c.h, IGM_F32_PATH if f32 else 0, ctypes.byref(prm), S, N, xyz.ctypes.data,
+                                    _np(radii, np.float32).ctypes.data, _np(flags, np.uint32).ctypes.data,
+                                    shared.ctypes.data if len(shared) else None, len(shared), _lib.ptr(sptr),
+                                    _lib.ptr(sb), float(evf), float(envf), f.ctypes.data, e.ctypes.data)
+        c.check(rc, 'igm_mstep_forces')
     return f, e
 
 
 def md(params, xyz, v, radii, flags, shared_bonds, sbond_ptr, sbonds, evf, envf, t0, t1, xmax, nsteps,
-       ctx=None, device=0):
+       ctx=None, device=0, anchors=None):
     """One 'run nsteps' segment (nve/limit + temp/rescale) from given velocities."""
     c = ctx or _lib.context(device)
     xyz = np.array(xyz, np.float32, order='C', copy=True)
@@ -112,11 +143,13 @@ def md(params, xyz, v, radii, flags, shared_bonds, sbond_ptr, sbonds, evf, envf,
     S, N = xyz.shape[0], xyz.shape[1]
     shared, sptr, sb = _bonds_args(shared_bonds, sbond_ptr, sbonds, S)
     prm = _prm(params, flags)
-    rc = c.lib.igm_mstep_md(c.h, 0, ctypes.byref(prm), S, N, xyz.ctypes.data, v.ctypes.data,
-                            _np(radii, np.float32).ctypes.data, _np(flags, np.uint32).ctypes.data,
-                            shared.ctypes.data if len(shared) else None, len(shared), _lib.ptr(sptr),
-                            _lib.ptr(sb), float(evf), float(envf), float(t0), float(t1), float(xmax), int(nsteps))
-    c.check(rc, 'igm_mstep_md')
+    with _anchored(c, anchors, S):
+        rc = c.lib.igm_mstep_md(c.h, 0, ctypes.byref(prm), S, N, xyz.ctypes.data, v.ctypes.data,
+                                _np(radii, np.float32).ctypes.data, _np(flags, np.uint32).ctypes.data,
+                                shared.ctypes.data if len(shared) else None, len(shared), _lib.ptr(sptr),
+                                _lib.ptr(sb), float(evf), float(envf), float(t0), float(t1), float(xmax),
+                                int(nsteps))
+        c.check(rc, 'igm_mstep_md')
     return xyz, v
 
 
@@ -187,4 +220,17 @@ def violations(params, xyz, radii, flags, shared_bonds, shared_class, sbond_ptr,
                                     _lib.ptr(sptr), _lib.ptr(sb), _lib.ptr(scl), len(ccr), ccr.ctypes.data,
                                     _lib.ptr(esc), float(tol), stats.ctypes.data)
     c.check(rc, 'igm_mstep_violations')
+    return stats
+
+
+def anchor_violations(xyz, tol, anchors, ctx=None, device=0):
+    """The ModelingStep record of the position anchors (vstat key 'Tracing'): (S, 104) int64,
+    the record layout of violations().  anchors = (ptr, igm_anchor array)."""
+    c = ctx or _lib.context(device)
+    xyz = _np(xyz, np.float32)
+    S, N = xyz.shape[0], xyz.shape[1]
+    stats = np.zeros((S, REC), np.int64)
+    with _anchored(c, anchors, S):
+        rc = c.lib.igm_mstep_anchor_violations(c.h, 0, S, N, xyz.ctypes.data, float(tol), stats.ctypes.data)
+        c.check(rc, 'igm_mstep_anchor_violations')
     return stats

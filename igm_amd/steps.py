@@ -540,8 +540,8 @@ def modeling_spec(cfg, sids):
     implement raise NotImplementedError -- none is dropped silently."""
     rs = cget(cfg, 'model/restraints', {}) or {}
     R = cfg.get('restraints', {}) or {}
-    if 'tracing' in R:  # the reference has no A-step for it (bin/igm-run:122-136)
-        raise NotImplementedError('restraints/tracing is not implemented on the hip kernel')
+    if 'tracing' in R:
+        tracing_assignment_file(cfg)  # (raises before any other key is read)
     if 'nucleolus' in rs or 'nuclDamID' in R:
         # ModelingStep.py:306-371 runs only on an exp_map nucleus: it logs an undefined name
         # (:326) and adds an undefined restraint (:347-370) otherwise (D8).  Checked before
@@ -591,7 +591,35 @@ def modeling_spec(cfg, sids):
     if 'FISH' in R:
         spec['fish'] = {'data': _h5_tree(fish_assignment_path(cfg)), 'rtype': R['FISH']['rtype'],
                         'tol': float(cfg['runtime']['FISH']['tol']), 'k': float(R['FISH']['kspring'])}
+    if 'tracing' in R:  # ModelingStep.py:281-300
+        spec['tracing'] = {'data': tracing_data(cfg), 'tol': float(cfg['runtime']['tracing']['tol']),
+                           'k': float(R['tracing']['kspring'])}
     return spec
+
+
+def tracing_assignment_file(cfg):
+    """restraints/tracing/assignment_file; a tracing section without one cannot be modelled:
+    the reference has no assignment step that could produce the file (bin/igm-run:122-136,
+    its ImagedLociAssignmentStep is commented out)."""
+    path = (cfg.get('restraints', {}).get('tracing') or {}).get('assignment_file')
+    if not path:
+        raise NotImplementedError('restraints/tracing without assignment_file is not implemented on the hip kernel: '
+                                  'the reference has no assignment step that could produce the file')
+    return path
+
+
+_TRACING = {}
+
+
+def tracing_data(cfg):
+    """the tracing assignment of the config (read once per file version)"""
+    from . import tracing as T
+    path = tracing_assignment_file(cfg)
+    key = (path, os.path.getmtime(path))
+    if key not in _TRACING:
+        _TRACING.clear()
+        _TRACING[key] = T.read_assignment(path)
+    return _TRACING[key]
 
 
 # ------------------------------------------------------------------ kernels

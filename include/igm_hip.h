@@ -353,6 +353,35 @@ typedef struct {
     int32_t cg_iters, cg_evals, stop_reason, nrebuild;
 } igm_opt_info;
 
+/* Position anchors (chromatin tracing, igm/restraints/tracing.py): a harmonic upper bound
+ * between an atom and a fixed point, per structure -- the reference's DUMMY_STATIC centroid
+ * with HarmonicUpperBound(centroid, locus, radial_tolerance, k), without the centroid atom.
+ *   r = |x_atom - (x, y, z)|:  E = k (r - r0)^2 for r > r0, else 0 (the igm_bond form); the
+ *   force on the atom follows from E and is 0 at r = 0.  The target is f32 (as a dummy's
+ *   position would be) and no stage's envelope factor scales it.
+ * The energy is bond energy (igm_opt_info.bond_energy, energies[2]).  An atom may carry
+ * several anchors, evaluated in the order given; an IGM_ATOM_FIXED atom contributes energy
+ * and takes no force.  igm_opt_info.temp (thermo temp of group all) counts every anchor of
+ * the structure as one more motionless atom, dof = 3 (natom + n_anchor) - 3, which is the
+ * reference's count with one centroid atom per restraint; the reference merges consecutive
+ * coincident dummies (lammps_model.py:303-312) and that merge is not restated.  Anchors are
+ * not atoms: temp/rescale, velocity create and the CG degrees of freedom do not see them. */
+typedef struct {
+    uint32_t atom;
+    float x, y, z; /* target                                             */
+    float r0, k;   /* E = k (r - r0)^2 beyond r0                         */
+} igm_anchor;      /* 24 bytes */
+
+/* Stage anchors in the context for the igm_mstep_* calls that follow, as igm_mstep_set_volumes
+ * stages maps: structure s of a batch has anchors[anchor_ptr[s] .. anchor_ptr[s+1]) (host
+ * pointers, copied).  nstruct = 0 clears.  IGM_E_INVALID here: anchor_ptr not monotone from 0,
+ * r0 < 0, a non-finite target, r0 or k.  IGM_E_INVALID at the run: nstruct different from the
+ * batch of the call, atom >= natom.  igm_mstep_run, igm_mstep_forces (both paths) and
+ * igm_mstep_md apply the staged anchors; with nothing staged they launch the kernels of a
+ * library without anchors.  Device memory: 24 B per anchor and 4 B per (structure, atom),
+ * allocated before the population engine's memory check reads the free HBM. */
+int igm_mstep_set_anchors(igm_ctx* ctx, int32_t nstruct, const int64_t* anchor_ptr, const igm_anchor* anchors);
+
 /* Run the whole protocol for `nstruct` structures of `natom` atoms each.
  *   xyz       (nstruct, natom, 3) f32, in/out
  *   radii     (natom) f32; atom_flags (natom), or (nstruct, natom) with IGM_MSTEP_STRUCT_FLAGS
@@ -448,6 +477,13 @@ int igm_mstep_violations(igm_ctx* ctx, uint32_t flags, const igm_mstep_params* p
                          const int64_t* sbond_ptr, const igm_bond* sbonds, const int32_t* sclass,
                          int32_t nclass_bonds, const double* class_cr, const double* env_scale, double tol,
                          int64_t* stats);
+
+/* The ModelingStep record of the staged anchors (vstat key 'Tracing', ModelingStep.py:281-300):
+ * stats (nstruct, 104) int64, the record layout above; ratio = (r - r0) / r0 past the bound
+ * with r the float32 norm, 0 when r0 == 0 (forces.py:131-139); n_imposed = the structure's
+ * anchors.  xyz (nstruct, natom, 3) f32. */
+int igm_mstep_anchor_violations(igm_ctx* ctx, uint32_t flags, int32_t nstruct, int32_t natom,
+                                const float* xyz, double tol, int64_t* stats);
 
 #ifdef __cplusplus
 }
