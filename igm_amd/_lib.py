@@ -142,6 +142,10 @@ SIGNATURES = {
                                     _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _f64, _vp]),
     'igm_mstep_set_anchors': (_i32, [_vp, _i32, _vp, _vp]),
     'igm_mstep_anchor_violations': (_i32, [_vp, _u32, _i32, _i32, _vp, _f64, _vp]),
+    'igm_report_levels': (_i32, [_vp, _u32, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp]),
+    'igm_report_rg': (_i32, [_vp, _u32, _vp, _i32, _i32, _vp, _vp, _i32, _vp]),
+    'igm_report_lamina': (_i32, [_vp, _u32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
+    'igm_report_distance_map': (_i32, [_vp, _u32, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp]),
 }
 
 _lib = None

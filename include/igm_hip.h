@@ -485,6 +485,71 @@ int igm_mstep_violations(igm_ctx* ctx, uint32_t flags, const igm_mstep_params* p
 int igm_mstep_anchor_violations(igm_ctx* ctx, uint32_t flags, int32_t nstruct, int32_t natom,
                                 const float* xyz, double tol, int64_t* stats);
 
+/* ---- population report (the igm/report modules, driven by bin/igm-report) ----------
+ * The structural numbers of the report on the bead-major .hss population: xyz is
+ * always (nbead, nstruct, 3) f32.  xyz and the outputs follow `flags`
+ * (IGM_DEVICE_PTRS); semiaxes, edges, CSR arrays, hap_chrom and inv_denoms are host
+ * pointers in every mode.  Every floating-point sum has a fixed order: a rerun is
+ * bitwise equal. */
+
+/* Radial levels: get_radial_level (igm/report/radials.py:15-39), plot_radial_density
+ * (:69-87) and report_shells (igm/report/shells.py:9-43).  The level of (bead,
+ * structure) is sqrt(((x/a)^2 + (y/b)^2) + (z/c)^2) in float64 on the widened
+ * coordinates, bit-equal to np.sqrt(np.sum(np.square(crd / semiaxes), axis=1)).
+ * Outputs, each may be NULL:
+ *   level_mean     (nbead) f64: the mean over the structures (summed in structure order)
+ *   density_counts (nbins) int64: np.histogram of all nbead * nstruct levels on the
+ *                  nbins + 1 density_edges (np.linspace(0, vmax, nbins + 1)): bin k holds
+ *                  edges[k] <= v < edges[k+1], the last bin is closed, the rest is dropped
+ *   shell_mean     (nstruct, nshell) f64 and shell_hist (nshell, hnbins) int64 on the
+ *                  hnbins + 1 shell_edges: per structure the levels are ranked, shell j
+ *                  holds the ranks [int(j n / nshell), int((j+1) n / nshell)) (np.partition
+ *                  at those ranks); its mean, and its histogram summed over the structures.
+ *                  An empty shell (nbead < nshell) gives NaN and no counts.
+ * nbead <= 65535, nshell <= 256. */
+int igm_report_levels(igm_ctx* ctx, uint32_t flags,
+                      const float* xyz, int32_t nbead, int32_t nstruct, const double* semiaxes,
+                      double* level_mean,
+                      const double* density_edges, int32_t nbins, int64_t* density_counts,
+                      int32_t nshell, double* shell_mean,
+                      const double* shell_edges, int32_t hnbins, int64_t* shell_hist);
+
+/* Radius of gyration: rg / get_chroms_rgs (igm/report/radius_of_gyration.py:9-41).
+ * The chains are a CSR (chain_ptr (nchain + 1), chain_idx bead indices) in
+ * index.get_chrom_pos(chrom, copy) order.  rg (nchain, nstruct) f64 =
+ * sqrt(sum |p - mean(p)|^2 / n), two passes in float64 over the float32 coordinates in
+ * bead order (the reference sums in float32: equal to its rounding).  An empty chain
+ * gives NaN. */
+int igm_report_rg(igm_ctx* ctx, uint32_t flags,
+                  const float* xyz, int32_t nbead, int32_t nstruct,
+                  const int32_t* chain_ptr, const int32_t* chain_idx, int32_t nchain, double* rg);
+
+/* Lamina (DamID) contacts: report_damid (igm/report/damid.py:32-51) with
+ * snormsq_ellipse (igm/report/utils.py:73-89) as NumPy 2 evaluates it.  inv_denoms
+ * (nhap, 3) f64 holds the three denominators of every locus,
+ * (semiaxes * (1 - contact_range) - r)**2 with r the radius of its first copy; the
+ * value of a copy in a structure is (xx/A + yy/B) + zz/C with xx = fl32(x * x) widened
+ * to float64.  counts (nhap) int64 = the number of (copy, structure) with value >= 1;
+ * the caller divides by nstruct and the copy count (:50). */
+int igm_report_lamina(igm_ctx* ctx, uint32_t flags,
+                      const float* xyz, int32_t nbead, int32_t nstruct,
+                      const int32_t* copy_ptr, const int32_t* copy_idx, int32_t nhap,
+                      const double* inv_denoms, int64_t* counts);
+
+/* Average distance map: create_average_distance_map (igm/report/distance_map.py:5-22).
+ * dmap (nhap, nhap) f64.  For a copy pair (k, m) the float32 norms
+ * sqrt((dx*dx + dy*dy) + dz*dz) (np.linalg.norm(axis=1) on float32) are averaged over
+ * the structures in float64, in structure order; entry (a, b), a < b, is the mean of
+ * those means over the k-th copy with the k-th copy when hap_chrom[a] == hap_chrom[b]
+ * (the reference's zip: up to the smaller copy count), else over every copy of a with
+ * every copy of b.  The reference leaves the diagonal and the lower triangle
+ * uninitialised: here the diagonal is 0 and the lower triangle mirrors the upper.  An
+ * entry without a copy pair is NaN.  copy_ptr / copy_idx: CSR of index.copy_index. */
+int igm_report_distance_map(igm_ctx* ctx, uint32_t flags,
+                            const float* xyz, int32_t nbead, int32_t nstruct,
+                            const int32_t* copy_ptr, const int32_t* copy_idx, const int32_t* hap_chrom,
+                            int32_t nhap, double* dmap);
+
 #ifdef __cplusplus
 }
 #endif
