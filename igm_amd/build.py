@@ -33,6 +33,7 @@ SOURCES = {
     'restraints.hip': ['-ffp-contract=off'],
     # the report restates NumPy f32 / f64 arithmetic; its f32 sqrt stays correctly rounded
     'report.hip': ['-ffp-contract=off'],
+    'report_hic.hip': ['-ffp-contract=off'],
 }
 # host-only C++ (no device code): the .hss / actdist.hdf5 reader and writer
 HOST_SOURCES = {'h5io.cpp': []}

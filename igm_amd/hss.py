@@ -174,6 +174,75 @@ def read_hcs(path):
                 'nbin': int(f.attrs('/').get('nbin', len(f.read('index/chrom'))))}
 
 
+def haploid_index(path):
+    """(index, genome) trees for write_hcs from a population .hss: the index of the first
+    copy of every haploid locus, in locus order (a single-copy index), and the genome
+    group as stored (None when the file has none)."""
+    with h5.File(path) as f:
+        idx = read_tree(f, 'index')
+        genome = read_tree(f, 'genome') if 'genome/' in f.keys('/') else None
+    copy_ptr, copy_idx = copy_index_arrays(idx['copy_index'])
+    first = copy_idx[copy_ptr[:-1]]
+    nhap = len(first)
+    one = np.arange(nhap + 1, dtype=np.int32)
+
+    def pick(k):
+        return np.asarray(idx[k])[first] if k in idx and len(np.asarray(idx[k])) == len(idx['chrom']) else None
+
+    index = index_tree(np.asarray(idx['chrom'])[first], np.zeros(nhap, np.int32), one, one[:-1], start=pick('start'),
+                       end=pick('end'), chromstr=pick('chromstr'), label=pick('label'))
+    return index, genome
+
+
+def write_hcs(path, matrix, nstruct=None, chrom=None, index=None, genome=None):
+    """A .hcs with the groups read_hcs reads: matrix/{indptr, indices, data}, index/*,
+    genome/* and the nbin attribute.  matrix: (nbin, nbin) symmetric, either probabilities
+    (floating point) or contact counts (integers; nstruct is then required and the value is
+    min(count, nstruct) / nstruct in float64, rounded to float32).  Stored: the upper
+    triangle with the diagonal, nonzeros only, float32.  index: the haploid index tree
+    (index_tree / haploid_index), or built from chrom (nbin,); genome: a dict of its
+    datasets or None.  alabtools is absent, so its exact .hcs layout beyond what read_hcs
+    consumes (for instance a separate matrix/diagonal, attributes of the matrix group) is
+    unpinned: a file written here is read back by this project, not known to be read by
+    alabtools."""
+    m = np.asarray(matrix)
+    if m.ndim != 2 or m.shape[0] != m.shape[1]:
+        raise ValueError('matrix must be square')
+    nbin = m.shape[0]
+    if np.issubdtype(m.dtype, np.integer):
+        if nstruct is None or nstruct < 1:
+            raise ValueError('contact counts need nstruct >= 1')
+    elif nstruct is not None:
+        raise ValueError('nstruct is for integer contact counts; probabilities are stored as given')
+    indptr = np.zeros(nbin + 1, np.int64)
+    cols, vals = [], []
+    for a in range(nbin):  # row by row: no second dense matrix
+        row = m[a, a:]
+        if nstruct is not None:
+            row = np.clip(row, 0, nstruct) / np.float64(nstruct)
+        row = row.astype(np.float32)
+        nz = np.flatnonzero(row)
+        cols.append((nz + a).astype(np.int32))
+        vals.append(row[nz])
+        indptr[a + 1] = indptr[a] + len(nz)
+    if index is None:
+        if chrom is None:
+            raise ValueError('write_hcs needs an index tree or the chromosome of every bin')
+        one = np.arange(nbin + 1, dtype=np.int32)
+        index = index_tree(np.asarray(chrom, np.int32), np.zeros(nbin, np.int32), one, one[:-1])
+    if len(index['chrom']) != nbin:
+        raise ValueError('the index has %d entries, the matrix %d bins' % (len(index['chrom']), nbin))
+    tree = {'@nbin': np.int32(nbin), 'index': index,
+            'matrix': {'indptr': indptr.astype(np.int32 if indptr[-1] < 2**31 else np.int64),
+                       'indices': np.concatenate(cols) if cols else np.zeros(0, np.int32),
+                       'data': np.concatenate(vals) if vals else np.zeros(0, np.float32)}}
+    if genome is not None:
+        tree['genome'] = genome
+    tmp = path + '.tmp'
+    h5.write(tmp, tree)
+    os.replace(tmp, path)
+
+
 def write_actdist(path, rows):
     """actdist.hdf5 with the four datasets of ActivationDistanceStep.reduce (:285-289)"""
     tmp = path + '.tmp'

@@ -11,11 +11,18 @@ bin/igm-report) computed on the GPU from the bead-major population.
                           igm_report_lamina
   average_distance_map -- create_average_distance_map (report/distance_map.py:5-22),
                           igm_report_distance_map
+  hic_statistics / hic_correlations / hic_comparison
+                       -- report_hic (report/hic.py:16-180): the Pearson correlations between
+                          the input Hi-C matrix and the simulated contact map, per chromosome
+                          and inter-chromosomal, over all / imposed / non-imposed entries, and
+                          the two 2-D histograms of plots.py, igm_report_hic
   report_population    -- the numeric files bin/igm-report leaves in its output directory
                           (names and formats of the reference); plots, images and the HTML
                           page stay with the reference
 
     python -m igm_amd.report HSS [-c CONFIG] [-l LABEL] [--semiaxes A B C] [--steps ...] [-o DIR]
+                             [--hic HCS] [--hic-sigma S] [--hic-inter-sigma S] [--hic-intra-sigma S]
+                             [--hic-contact-range R]
 
 Every function takes the population as host arrays -- xyz (nbead, nstruct, 3) float32, the
 .hss layout -- or as a steps.PopulationStore, which then also supplies the index arrays
@@ -31,6 +38,7 @@ import numpy as np
 from . import _lib
 
 STEPS = ('rgs', 'shells', 'radials', 'damid', 'distance_map')
+OPTIONAL_STEPS = ('hic',)                    # accepted in `steps`, not run by default
 DEFAULT_SEMIAXES = (5000.0, 5000.0, 5000.0)  # report_radials / report_shells / report_damid
 DEFAULT_DAMID_CONTACT_RANGE = 0.05           # restraints/DamID/contact_range of the reference's config defaults
 
@@ -244,6 +252,163 @@ def average_distance_map(pop, copy_ptr=None, copy_idx=None, hap_chrom=None, ctx=
     return out
 
 
+# ------------------------------------------------------------------ the Hi-C comparison
+HIC_MASKS = ('all', 'restrained', 'non_restrained')
+
+
+def hic_edges():
+    """(log_edges, lin_edges) of logloghist2d and density_histogram_2d as report_hic calls
+    them (bins=(100, 100), ranges (1e-3, 1); report/plots.py:20-21, 89-90), the same on both
+    axes: 100 logarithmic bins and -- np.linspace(x0, x1, bins) -- 99 linear ones."""
+    return (np.logspace(np.log10(1e-3), np.log10(1), 100 + 1, base=10), np.linspace(1e-3, 1, 100))
+
+
+def _sigma(v):
+    """a sigma that is None, NaN or <= 0 is 'not given' (report_hic tests `if sigma:`)"""
+    if v is None:
+        return None
+    v = float(v)
+    return v if v > 0 else None
+
+
+def _hcs(matrix):
+    if isinstance(matrix, (str, os.PathLike)):
+        from . import hss
+        matrix = hss.read_hcs(os.fspath(matrix))
+    return matrix
+
+
+def hic_statistics(counts, nstruct, matrix, hap_chrom, intra_sigma=None, inter_sigma=None, log_edges=None,
+                   lin_edges=None, nchrom=None, flags=0, ctx=None, device=0):
+    """The raw igm_report_hic call: the sufficient statistics of the comparison between the
+    haploid contact counts (nhap, nhap) int32 of evaluation.haploid_counts and the input
+    matrix (the read_hcs dict: indptr, indices, data of the upper triangle).
+
+    log_edges / lin_edges: None for no histogram, an edge array for both axes, or a pair
+    (edges_x, edges_y).  With flags = IGM_DEVICE_PTRS, counts and the matrix's indices and
+    data are device tensors.  Returns a dict of arrays over the nchrom + 1 populations (the
+    chromosomes, then inter): n, dense_sums, sparse_ints, sparse_sumx, means, centred (the
+    layouts of include/igm_hip.h), log_hist / lin_hist (ny, nx) int64 or None, nstruct and
+    the sigmas used (None = not given)."""
+    hap_chrom = np.ascontiguousarray(hap_chrom, np.int32)
+    nhap = len(hap_chrom)
+    indptr = np.ascontiguousarray(matrix['indptr'], np.int64)
+    indices, data = matrix['indices'], matrix['data']
+    if not (flags & _lib.IGM_DEVICE_PTRS):
+        counts = np.ascontiguousarray(counts, np.int32)
+        indices = np.ascontiguousarray(indices, np.int32)
+        data = np.ascontiguousarray(data, np.float32)
+        if len(indices) != len(data):
+            raise ValueError('the matrix needs one value per column index')
+    if tuple(counts.shape) != (nhap, nhap) or indptr.shape != (nhap + 1,):
+        raise ValueError('counts must be (nhap, nhap) and indptr (nhap + 1,) for the %d entries of hap_chrom' % nhap)
+    if indptr[-1] > len(indices):
+        raise ValueError('indptr ends at %d, the matrix stores %d entries' % (indptr[-1], len(indices)))
+    if nchrom is None:
+        nchrom = int(hap_chrom.max()) + 1 if nhap else 0
+    P = int(nchrom) + 1
+    si, se = _sigma(intra_sigma), _sigma(inter_sigma)
+
+    def edges(e):
+        if e is None:
+            return None, None, None
+        ex, ey = e if isinstance(e, (tuple, list)) and len(e) == 2 and np.ndim(e[0]) == 1 else (e, e)
+        ex, ey = np.ascontiguousarray(ex, np.float64), np.ascontiguousarray(ey, np.float64)
+        return ex, ey, np.empty((len(ey) - 1, len(ex) - 1), np.int64)
+
+    lgx, lgy, lgh = edges(log_edges)
+    lix, liy, lih = edges(lin_edges)
+    dense = np.empty((P, 2), np.int64)
+    sparse = np.empty((P, 2, 3), np.int64)
+    sumx = np.empty((P, 2), np.float64)
+    means = np.empty((P, 3, 2), np.float64)
+    cent = np.empty((P, 3, 2), np.float64)
+    c = ctx or _lib.context(device)
+    lnx, lny, inx, iny = (0 if e is None else len(e) - 1 for e in (lgx, lgy, lix, liy))
+    rc = c.lib.igm_report_hic(c.h, int(flags), _lib.ptr(counts), nhap, int(nstruct), indptr.ctypes.data,
+                              _lib.ptr(indices), _lib.ptr(data), hap_chrom.ctypes.data, int(nchrom),
+                              0.0 if si is None else si, 0.0 if se is None else se,
+                              _lib.ptr(lgx), lnx, _lib.ptr(lgy), lny, _lib.ptr(lgh),
+                              _lib.ptr(lix), inx, _lib.ptr(liy), iny, _lib.ptr(lih),
+                              dense.ctypes.data, sparse.ctypes.data, sumx.ctypes.data, means.ctypes.data,
+                              cent.ctypes.data)
+    c.check(rc, 'igm_report_hic')
+    m = np.bincount(hap_chrom, minlength=int(nchrom)).astype(np.int64)
+    n = np.concatenate([m * m, [(nhap * nhap - int((m * m).sum())) // 2]]).astype(np.int64)
+    return {'n': n, 'dense_sums': dense, 'sparse_ints': sparse, 'sparse_sumx': sumx, 'means': means, 'centred': cent,
+            'log_hist': lgh, 'lin_hist': lih, 'nstruct': int(nstruct), 'intra_sigma': si, 'inter_sigma': se}
+
+
+def hic_correlations(stats):
+    """Pearson r of every (population, mask) from the statistics of hic_statistics:
+    {'intra': {mask: (nchrom,) float64}, 'inter': {mask: float}}, masks HIC_MASKS.
+
+    r = cross / sqrt(var_x * var_y) with cross = centred[.., 0], var_x = centred[.., 1] +
+    (n - n_stored) xbar^2 and var_y = (n sum c'^2 - (sum c')^2) / (n nstruct^2) computed
+    exactly on the integers and rounded once.  A set with fewer than 2 entries or a
+    constant side gives NaN (no warning); so does a mask whose sigma was not given."""
+    from fractions import Fraction
+    n_all, S = stats['n'], int(stats['nstruct'])
+    P = len(n_all)
+    r = np.full((P, 3), np.nan)
+    for p in range(P):
+        sig = stats['inter_sigma'] if p == P - 1 else stats['intra_sigma']
+        d1, d2 = (int(v) for v in stats['dense_sums'][p])
+        (w0, a0, b0), (w1, _, _) = ([int(v) for v in h] for h in stats['sparse_ints'][p])
+        na = int(n_all[p])
+        sets = ((na, d1, d2, w0 + w1), (w0, a0, b0, w0), (na - w0, d1 - a0, d2 - b0, w1))
+        for m, (n, s1, s2, nst) in enumerate(sets):
+            if n < 2 or (m > 0 and sig is None):
+                continue
+            var_y = float(Fraction(n * s2 - s1 * s1, n * S * S))
+            xbar = float(stats['means'][p, m, 1])
+            var_x = float(stats['centred'][p, m, 1]) + (n - nst) * (xbar * xbar)
+            if not (var_y > 0 and var_x > 0):
+                continue
+            r[p, m] = max(-1.0, min(1.0, float(stats['centred'][p, m, 0]) / np.sqrt(var_x * var_y)))
+    return {'intra': {k: r[:-1, m].copy() for m, k in enumerate(HIC_MASKS)},
+            'inter': {k: float(r[-1, m]) for m, k in enumerate(HIC_MASKS)}}
+
+
+def hic_comparison(pop, matrix, contact_range, intra_sigma=None, inter_sigma=None, radii=None, copy_ptr=None,
+                   copy_idx=None, hap_chrom=None, ctx=None, device=0):
+    """report_hic's numbers for a population: the contact counts at contact_range
+    (evaluation.haploid_counts; the restraint's contact_range unchanged, as report_hic passes
+    it to get_simulated_hic, hic.py:51 -- no 1 + EPS here), compared with the input matrix (a
+    read_hcs dict or the path of a .hcs).  Returns {'intra': {mask: per-chromosome array},
+    'inter': {mask: float}, 'log_hist', 'lin_hist' (int64, rows = output, columns = input),
+    'log_edges', 'lin_edges', 'counts'}.  The chromosomes are the ids 0 .. max(hap_chrom)."""
+    from . import evaluation
+    xyz, store = _population(pop)
+    radii = _pick(radii, store, 'radii')
+    copy_ptr, copy_idx = _csr(_pick(copy_ptr, store, 'copy_ptr'), _pick(copy_idx, store, 'copy_idx'), xyz.shape[0],
+                              'copy')
+    hap_chrom = np.ascontiguousarray(_pick(hap_chrom, store, 'hap_chrom'), np.int32)
+    matrix = _hcs(matrix)
+    nhap = len(copy_ptr) - 1
+    if hap_chrom.shape != (nhap,) or len(matrix['indptr']) != nhap + 1:
+        raise ValueError('hap_chrom and the input matrix must cover the %d haploid loci of the population' % nhap)
+    counts = evaluation.haploid_counts(xyz, radii, float(contact_range), copy_ptr, copy_idx, ctx=ctx, device=device)
+    log_edges, lin_edges = hic_edges()
+    stats = hic_statistics(counts, xyz.shape[1], matrix, hap_chrom, intra_sigma, inter_sigma, log_edges, lin_edges,
+                           ctx=ctx, device=device)
+    out = hic_correlations(stats)
+    out.update({'log_hist': stats['log_hist'], 'lin_hist': stats['lin_hist'], 'log_edges': log_edges,
+                'lin_edges': lin_edges, 'counts': counts})
+    return out
+
+
+def hic_correlation_texts(names, corr):
+    """(intra text, inter text): matrix_comparison/{intra,inter}_correlations.txt in
+    report_hic's formats (hic.py:88-94, 124-130); names: one per row of the intra arrays"""
+    intra = '# chrom all imposed non_imposed\n'
+    for k, c in enumerate(names):
+        x, y, z = (corr['intra'][m][k] for m in HIC_MASKS)
+        intra += f'{c:6s} {x:8.5f} {y:8.5f} {z:8.5f}\n'
+    inter = '# all imposed non_imposed\n' + '{:8.5f} {:8.5f} {:8.5f}\n'.format(*(corr['inter'][m] for m in HIC_MASKS))
+    return intra, inter
+
+
 # ------------------------------------------------------------------ the igm-report driver
 def _cfg_get(cfg, path, default=None):
     node = cfg
@@ -255,10 +420,32 @@ def _cfg_get(cfg, path, default=None):
 
 
 def parameters_from_config(cfg, basedir='.'):
-    """get_parameters_from_igm_config (bin/igm-report:103-128) for the steps built here:
-    {'semiaxes' or None, 'shape', 'damid': {'input_profile', 'contact_range'}}.  An exp_map
-    nucleus has no semiaxes: the entry stays None instead of the reference's 5000."""
+    """get_parameters_from_igm_config (bin/igm-report:103-169) for the steps built here:
+    {'semiaxes' or None, 'shape', 'damid': {'input_profile', 'contact_range'}, 'hic':
+    {'input_matrix', 'contact_range', 'inter_sigma', 'intra_sigma'}}.  An exp_map nucleus
+    has no semiaxes: the entry stays None instead of the reference's 5000.  The Hi-C sigmas
+    come from runtime/Hi-C/{inter,intra}_sigma, else the old runtime/Hi-C/sigma, else the
+    last entries of restraints/Hi-C/{inter,intra}_sigma_list, else of the old sigma_list."""
     out = {'semiaxes': None, 'shape': _cfg_get(cfg, 'model/restraints/envelope/nucleus_shape')}
+    if _cfg_get(cfg, 'restraints/Hi-C', False):
+        fpath = _cfg_get(cfg, 'restraints/Hi-C/input_matrix')
+        if fpath and not os.path.isabs(fpath):
+            fpath = os.path.abspath(os.path.join(basedir, fpath))
+        hic = {'input_matrix': fpath, 'contact_range': _cfg_get(cfg, 'restraints/Hi-C/contact_range'),
+               'inter_sigma': None, 'intra_sigma': None}
+        if _cfg_get(cfg, 'runtime/Hi-C/inter_sigma', False):
+            hic['inter_sigma'] = _cfg_get(cfg, 'runtime/Hi-C/inter_sigma')
+            hic['intra_sigma'] = _cfg_get(cfg, 'runtime/Hi-C/intra_sigma')
+        elif _cfg_get(cfg, 'runtime/Hi-C/sigma', False):
+            hic['inter_sigma'] = hic['intra_sigma'] = _cfg_get(cfg, 'runtime/Hi-C/sigma')
+        elif _cfg_get(cfg, 'restraints/Hi-C/inter_sigma_list', False):
+            hic['inter_sigma'] = _cfg_get(cfg, 'restraints/Hi-C/inter_sigma_list')[-1]
+            l2 = _cfg_get(cfg, 'restraints/Hi-C/intra_sigma_list', None)
+            if l2:
+                hic['intra_sigma'] = l2[-1]
+        elif _cfg_get(cfg, 'restraints/Hi-C/sigma_list', False):
+            hic['inter_sigma'] = hic['intra_sigma'] = _cfg_get(cfg, 'restraints/Hi-C/sigma_list')[-1]
+        out['hic'] = hic
     if _cfg_get(cfg, 'restraints/DamID', False):
         fpath = _cfg_get(cfg, 'restraints/DamID/input_profile')
         if fpath and not os.path.isabs(fpath):
@@ -272,6 +459,30 @@ def parameters_from_config(cfg, basedir='.'):
     elif _cfg_get(cfg, 'model/restraints/envelope/nucleus_radius', False):
         out['semiaxes'] = np.array([_cfg_get(cfg, 'model/restraints/envelope/nucleus_radius')] * 3, np.float64)
     return out
+
+
+def apply_hic_arguments(params, hic=None, hic_sigma=None, hic_inter_sigma=None, hic_intra_sigma=None,
+                        hic_contact_range=None):
+    """process_user_args (bin/igm-report:179-212) on the dict of parameters_from_config:
+    --hic names the input matrix (and opens a Hi-C section when the configuration had
+    none); --hic-sigma sets both sigmas, then --hic-inter-sigma / --hic-intra-sigma each
+    its own, then --hic-contact-range; all but --hic are ignored without a Hi-C section."""
+    params = dict(params)
+    if hic is not None:
+        params['hic'] = dict(params.get('hic') or {'contact_range': None, 'inter_sigma': None, 'intra_sigma': None})
+        params['hic']['input_matrix'] = os.path.abspath(hic)
+    if 'hic' not in params:
+        return params
+    params['hic'] = dict(params['hic'])
+    if hic_sigma is not None:
+        params['hic']['inter_sigma'] = params['hic']['intra_sigma'] = hic_sigma
+    if hic_inter_sigma is not None:
+        params['hic']['inter_sigma'] = hic_inter_sigma
+    if hic_intra_sigma is not None:
+        params['hic']['intra_sigma'] = hic_intra_sigma
+    if hic_contact_range is not None:
+        params['hic']['contact_range'] = hic_contact_range
+    return params
 
 
 def _hss_extras(path):
@@ -327,19 +538,27 @@ def pearson(x, y):
     return (r, float(pearsonr(x, y)[1]))
 
 
-def report_population(hss_path, cfg=None, out_dir=None, steps=STEPS, label='', semiaxes=None, ctx=None, device=0):
+def report_population(hss_path, cfg=None, out_dir=None, steps=STEPS, label='', semiaxes=None, ctx=None, device=0,
+                      hic=None, hic_sigma=None, hic_inter_sigma=None, hic_intra_sigma=None, hic_contact_range=None):
     """Write the numeric files of bin/igm-report for the population at hss_path into
     out_dir (default: QC_<label or file name> beside it) and return {relative name: path}.
 
     cfg: an IGM configuration (dict or JSON file); None looks for config_data in the .hss,
-    then for igm-config.json beside it (bin/igm-report:236-262).  steps: any of STEPS.
-    radials, shells and damid need semiaxes (resolve_semiaxes) and raise ValueError on an
-    exp_map nucleus without explicit ones."""
+    then for igm-config.json beside it (bin/igm-report:236-262).  steps: any of STEPS, and
+    'hic' (not run by default).  radials, shells and damid need semiaxes (resolve_semiaxes)
+    and raise ValueError on an exp_map nucleus without explicit ones.  hic needs the Hi-C
+    section of the configuration or the hic argument (the path of the input .hcs; the
+    hic_* arguments are the command line's, apply_hic_arguments) and raises ValueError
+    without one (the reference only logs).  It writes matrix_comparison/outmap.hcs,
+    intra_correlations.txt, inter_correlations.txt and -- this project's addition, the
+    reference only draws them -- the raw int64 histograms log_histogram2d.npy and
+    linear_histogram2d.npy.  When a sigma is not given its imposed / non_imposed columns
+    are nan (the reference then writes no intra rows and zeros in the inter row)."""
     from .steps import PopulationStore
     steps = tuple(steps.split(',')) if isinstance(steps, str) else tuple(steps)
-    unknown = [s for s in steps if s not in STEPS]
+    unknown = [s for s in steps if s not in STEPS + OPTIONAL_STEPS]
     if unknown:
-        raise ValueError('unknown report steps %s (known: %s)' % (unknown, ', '.join(STEPS)))
+        raise ValueError('unknown report steps %s (known: %s)' % (unknown, ', '.join(STEPS + OPTIONAL_STEPS)))
     hss_path = os.path.realpath(hss_path)
     store = PopulationStore(hss_path)
     env_shape = env_params = chrom_names = stored = None
@@ -357,6 +576,15 @@ def report_population(hss_path, cfg=None, out_dir=None, steps=STEPS, label='', s
             with open(os.path.join(basedir, 'igm-config.json')) as f:
                 cfg = json.load(f)
     params = parameters_from_config(cfg, basedir) if cfg is not None else {'semiaxes': None, 'shape': None}
+    params = apply_hic_arguments(params, hic, hic_sigma, hic_inter_sigma, hic_intra_sigma, hic_contact_range)
+    if 'hic' in steps:
+        hcfg = params.get('hic')
+        if not hcfg or not hcfg.get('input_matrix'):
+            raise ValueError('the hic step needs an input matrix: a restraints/Hi-C section in the configuration '
+                             'or --hic')
+        if hcfg.get('contact_range') is None:
+            raise ValueError('the hic step needs a contact range: restraints/Hi-C/contact_range or '
+                             '--hic-contact-range')
     sx = resolve_semiaxes((env_shape, env_params), params, semiaxes)
     needs = [s for s in steps if s in ('radials', 'shells', 'damid')]
     if sx is None and needs:
@@ -409,6 +637,26 @@ def report_population(hss_path, cfg=None, out_dir=None, steps=STEPS, label='', s
     if 'distance_map' in steps:
         np.save(path('distance_map/average%s.npy' % tag),
                 average_distance_map(xyz, store.copy_ptr, store.copy_idx, store.hap_chrom, **kw))
+    if 'hic' in steps:
+        from . import hss
+        hcfg = params['hic']
+        res = hic_comparison(xyz, hcfg['input_matrix'], float(hcfg['contact_range']), hcfg.get('intra_sigma'),
+                             hcfg.get('inter_sigma'), store.radii, store.copy_ptr, store.copy_idx, store.hap_chrom,
+                             **kw)
+        index, genome = hss.haploid_index(hss_path) if store.is_hss else (None, None)
+        hss.write_hcs(path('matrix_comparison/outmap%s.hcs' % tag), res['counts'], nstruct=xyz.shape[1],
+                      chrom=store.hap_chrom, index=index, genome=genome)
+        ids = np.unique(store.hap_chrom)
+        names = chrom_names if chrom_names is not None and len(chrom_names) >= len(ids) else \
+            ['chr%d' % (i + 1) for i in ids]
+        rows = {'intra': {m: res['intra'][m][ids] for m in HIC_MASKS}, 'inter': res['inter']}
+        intra, inter = hic_correlation_texts(names[:len(ids)], rows)
+        with open(path('matrix_comparison/intra_correlations%s.txt' % tag), 'w') as f:
+            f.write(intra)
+        with open(path('matrix_comparison/inter_correlations%s.txt' % tag), 'w') as f:
+            f.write(inter)
+        np.save(path('matrix_comparison/log_histogram2d%s.npy' % tag), res['log_hist'])
+        np.save(path('matrix_comparison/linear_histogram2d%s.npy' % tag), res['lin_hist'])
     return written
 
 
@@ -422,11 +670,18 @@ def main(argv=None):
     ap.add_argument('--steps', default=','.join(STEPS),
                     help='comma separated list of steps to perform (default: %(default)s)')
     ap.add_argument('-o', '--out-dir', help='Output directory')
+    ap.add_argument('--hic', help='Input matrix for HiC')
+    ap.add_argument('--hic-sigma', type=float, help='Probability cutoff for HiC')
+    ap.add_argument('--hic-inter-sigma', type=float, help='Inter-chromosomal probability cutoff for HiC')
+    ap.add_argument('--hic-intra-sigma', type=float, help='Intra-chromosomal probability cutoff for HiC')
+    ap.add_argument('--hic-contact-range', type=float, help='Probability cutoff for HiC')
     a = ap.parse_args(argv)
     if not os.path.isfile(a.hss):
         ap.error('Cannot find file %s' % a.hss)
     written = report_population(a.hss, cfg=a.config, out_dir=a.out_dir, steps=a.steps, label=a.label,
-                                semiaxes=a.semiaxes)
+                                semiaxes=a.semiaxes, hic=a.hic, hic_sigma=a.hic_sigma,
+                                hic_inter_sigma=a.hic_inter_sigma, hic_intra_sigma=a.hic_intra_sigma,
+                                hic_contact_range=a.hic_contact_range)
     for rel in sorted(written):
         print(written[rel])
     return 0

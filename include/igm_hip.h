@@ -550,6 +550,72 @@ int igm_report_distance_map(igm_ctx* ctx, uint32_t flags,
                             const int32_t* copy_ptr, const int32_t* copy_idx, const int32_t* hap_chrom,
                             int32_t nhap, double* dmap);
 
+/* Hi-C comparison: the numbers of report_hic (igm/report/hic.py:16-180) as sufficient
+ * statistics, from which the caller forms the Pearson correlations, and the two 2-D
+ * histograms of input against simulated probability (igm/report/plots.py:28, 98).  No
+ * dense floating-point matrix is built anywhere.
+ *
+ * counts (nhap, nhap) int32: the symmetric output of igm_contact_map_haploid; counts,
+ * indices and data follow `flags`.  The input matrix is the CSR hss.read_hcs returns, the
+ * upper triangle with the diagonal allowed: indptr (nhap + 1) int64, indices int32, data
+ * float32; stored zeros are legal and behave as zeros.  hap_chrom (nhap): any ids in
+ * [0, nchrom).  indptr, hap_chrom, the edges and every output are host pointers in every
+ * mode.  A sigma <= 0 or NaN means "not given": every stored entry then counts as below it.
+ *
+ * Per entry (a, b):  y = c' / nstruct (one float64 division) with c' = min(counts[a, b],
+ * nstruct) -- the clip of evaluation.contact_map decided on integers; a negative count
+ * reads as 0 -- and x = the stored float32 widened to float64, 0 where nothing is stored.
+ * Populations p: for a chromosome c every ordered entry with hap_chrom[a] == hap_chrom[b]
+ * == c (the full symmetric block with its diagonal, x1d.ravel() of hic.py:60-65: a stored
+ * off-diagonal entry has weight w = 2, a diagonal one w = 1, n = m^2 for m loci); p =
+ * nchrom is the inter population, the pairs a < b on two chromosomes
+ * (np.triu(getInterMask()), :99), w = 1.  Masks: all, restrained (x >= sigma of the
+ * population: intra_sigma or inter_sigma), non-restrained (the complement, with every
+ * entry that is not stored).
+ *
+ * Outputs:
+ *   dense_sums  (nchrom + 1, 2) int64    {sum c', sum c'^2} over the whole population
+ *   sparse_ints (nchrom + 1, 2, 3) int64 over the stored entries with x >= sigma (half 0)
+ *               and x < sigma (half 1): {sum w, sum w c', sum w c'^2}
+ *   sparse_sumx (nchrom + 1, 2) f64      sum of w x over the two halves
+ *   means       (nchrom + 1, 3, 2) f64   per mask (all, restrained, non-restrained)
+ *               {ybar, xbar}: ybar = sum c' / (n nstruct), the exact integer quotient
+ *               rounded once; xbar = sum x / n, one float64 division; n and the sums of the
+ *               mask 'all' are the dense ones (sum x over both halves, half 0 first), of
+ *               'restrained' half 0, of 'non-restrained' dense minus half 0 (sum x: half 1);
+ *               an empty set has 0
+ *   centred     (nchrom + 1, 3, 2) f64   over the stored entries of the mask
+ *               {sum (w x) (y - ybar), sum w ((x - xbar) (x - xbar))}.  The first is the
+ *               whole cross term (the entries that are not stored have x = 0 and sum (y -
+ *               ybar) = 0); the caller adds (n - n_stored) xbar^2 to the second.
+ *   log_hist (log_ny, log_nx), lin_hist (lin_ny, lin_nx) int64, each may be NULL:
+ *               np.histogram2d(y, x, bins=(edges_y, edges_x)) over the whole symmetric
+ *               matrix (an off-diagonal entry counts twice): edges[k] <= v < edges[k+1],
+ *               the last bin closed, the rest dropped; rows = output, columns = input.
+ *               Only stored entries are binned: a lowest edge <= 0 is IGM_E_UNSUPPORTED.
+ * Integer sums use integer atomics (exact in any order).  Every float64 sum has a fixed
+ * order: a row is walked by 64 lanes (entry k of the row by lane k mod 64), the lanes are
+ * added by a shuffle tree (offsets 32, 16, .. 1); the per-row sums go to a scratch buffer
+ * and a second step adds them per population: thread t of 256 the rows t, t + 256, .. in
+ * ascending order, then the 256 partial sums by the same tree per wave and the waves in order.
+ * Compiled with -ffp-contract=off.  IGM_E_INVALID: indptr not non-decreasing from 0, a
+ * column outside [row, nhap), hap_chrom outside [0, nchrom), nstruct < 1, edges not
+ * strictly increasing; IGM_E_UNSUPPORTED: nhap^2 nstruct^2 >= 2^63.
+ *
+ * Unpinned (alabtools -- Contactmatrix.toarray, cm[c], getInterMask, get_simulated_hic --
+ * is absent): the symmetric-with-diagonal reading of toarray(), the clip to [0, 1], the
+ * '<=' of the contact test, float64 in the correlation (scipy takes the inputs' dtype). */
+int igm_report_hic(igm_ctx* ctx, uint32_t flags,
+                   const int32_t* counts, int32_t nhap, int32_t nstruct,
+                   const int64_t* indptr, const int32_t* indices, const float* data,
+                   const int32_t* hap_chrom, int32_t nchrom, double intra_sigma, double inter_sigma,
+                   const double* log_edges_x, int32_t log_nx, const double* log_edges_y, int32_t log_ny,
+                   int64_t* log_hist,
+                   const double* lin_edges_x, int32_t lin_nx, const double* lin_edges_y, int32_t lin_ny,
+                   int64_t* lin_hist,
+                   int64_t* dense_sums, int64_t* sparse_ints, double* sparse_sumx, double* means,
+                   double* centred);
+
 #ifdef __cplusplus
 }
 #endif
