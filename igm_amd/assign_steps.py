@@ -9,6 +9,8 @@ the GPU kernels of this package (igm_amd.damid, .fish, .sprite, .polymer).
   FishAssignmentStep           igm/steps/FishAssignmentStep.py:82-389
   SpriteAssignmentStep         igm/steps/SpriteAssignmentStep.py:20-263
   PolymerAssignmentStep        igm/steps/PolymerAssignmentStep.py:35-206
+  TracingAssignmentStep        no reference class (bin/igm-run:135 leaves it commented out):
+                               imaged traces -> the M-step's tracing assignment file
 
 Batches are GPU-sized (kernel_opts/hip: one launch covers thousands of loci or
 clusters) instead of one process per 100 loci.  The reference draws its SPRITE
@@ -424,5 +426,100 @@ class PolymerAssignmentStep(Step):
              os.path.join(self._dir(), self.cfg['restraints']['polymer']['assignment_file']))
 
 
+# ------------------------------------------------------------------ chromatin tracing
+class TracingAssignmentStep(Step):
+    """Chromatin tracing assignment (no counterpart in the reference: bin/igm-run:135 leaves
+    `ImagedLociAssignmentStep` commented out): every imaged trace of
+    restraints/tracing/input_file is given the (structure, copy) of the current population it
+    superposes best on -- the costs and the keep_best candidates on the GPU, the one-trace-per-
+    slot greedy assignment and the Kabsch targets on the host (igm_amd.tracing)."""
+
+    def __init__(self, cfg):
+        rt = _runtime(cfg, 'tracing')
+        if 'tol_list' not in rt:
+            rt['tol_list'] = list(cfg['restraints']['tracing']['tol_list'])
+        if 'tol' not in rt:
+            rt['tol'] = rt['tol_list'].pop(0)
+        super(TracingAssignmentStep, self).__init__(cfg)
+
+    def name(self):
+        return 'TracingAssignmentStep (tol={:.2f}, iter={:s})'.format(
+            cget(self.cfg, 'runtime/tracing/tol', -1), str(cget(self.cfg, 'runtime/opt_iter', 'N/A')))
+
+    def _dir(self):
+        d = make_absolute_path(cget(self.cfg, 'restraints/tracing/tmp_dir', 'tracing'),
+                               cget(self.cfg, 'parameters/tmp_dir', 'tmp'))
+        os.makedirs(d, exist_ok=True)
+        return d
+
+    def _path(self):
+        return os.path.join(self._dir(), 'tracing_assignment.h5')
+
+    def _traces(self, store):
+        from . import tracing
+        return tracing.read_traces(self.cfg['restraints']['tracing']['input_file'], store)
+
+    def setup(self):
+        store = PopulationStore(self.cfg['optimization']['structure_output'])
+        T = len(self._traces(store)['trace_ptr']) - 1
+        bs = int(cget(self.cfg, 'optimization/kernel_opts/hip/tracing_batch', 1 << 14))
+        self.argument_list = [{'batch': b, 't0': t0, 't1': min(t0 + bs, T),
+                               'out': os.path.join(self.tmp_dir, '%s.%d.tracing.npz' % (self.uid, b))}
+                              for b, t0 in enumerate(range(0, T, bs))]
+        self.tmp_extensions = ['.npz']
+
+    def task(self, batch, device):
+        """the batch's keep_best candidates as s * C + k with C the model's largest copy count
+        (one encoding for all batches, whatever the copy counts of a batch's own traces)"""
+        from . import tracing
+        store = PopulationStore(self.cfg['optimization']['structure_output'])
+        traces = self._traces(store)
+        S = store.nstruct
+        kb = min(int(rget(self.cfg, 'restraints/tracing/keep_best', 50)), S * int(traces['ncopy'].min()))
+        sub = tracing.slice_traces(traces, batch['t0'], batch['t1'])
+        cand, rmsd = _kernel(self.cfg, 'tracing_assign')(store, sub, kb, device)
+        cb, C = int(sub['ncopy'].max()), int(np.diff(store.copy_ptr).max())
+        cand = np.asarray(cand, np.int64)
+        tmp = batch['out'] + '.part.npz'
+        np.savez(tmp, cand=(cand // cb) * C + cand % cb, rmsd=np.asarray(rmsd, np.float32))
+        os.replace(tmp, batch['out'])
+
+    def reduce(self):
+        """greedy assignment over all batches, the targets of the assigned traces ->
+        <tmp_dir>/tracing/tracing_assignment.h5 (igm_amd.tracing.write_assignment); the
+        previous file kept as tracing_assignment.h5.tol_<tol>.iter_<n>"""
+        from . import tracing
+        store = PopulationStore(self.cfg['optimization']['structure_output'])
+        traces = self._traces(store)
+        T = len(traces['trace_ptr']) - 1
+        C = int(np.diff(store.copy_ptr).max())
+        res = [np.load(b['out']) for b in self.argument_list]
+        cand = np.concatenate([r['cand'] for r in res]) if res else np.zeros((0, 1), np.int64)
+        rmsd = np.concatenate([r['rmsd'] for r in res]) if res else np.zeros((0, 1), np.float32)
+        pick = tracing.greedy_assignment(cand, rmsd, traces['chrom'])
+        took = np.where(pick >= 0, cand[np.arange(T), np.maximum(pick, 0)], -1) if T else np.zeros(0, np.int64)
+        structure, copy = np.where(took >= 0, took // C, -1), np.where(took >= 0, took % C, -1)
+        target, fit, _ = tracing.aligned_targets(store.coordinates(), store.copy_ptr, store.copy_idx, traces,
+                                                 structure, copy)
+        path = self._path()
+        suffix = ['tol_{:.4f}'.format(cget(self.cfg, 'runtime/tracing/tol'))]
+        if 'opt_iter' in self.cfg['runtime']:
+            suffix.append('iter_{}'.format(self.cfg['runtime']['opt_iter']))
+        _rotate(cget(self.cfg, 'runtime/tracing/assignment_file', None), path, suffix)
+        tracing.write_assignment(path, traces, store.copy_ptr, store.copy_idx, structure, copy, target, fit)
+        cset(self.cfg, 'runtime/tracing/assignment_file', path)
+        cset(self.cfg, 'runtime/tracing/n_unassigned', int(np.count_nonzero(pick < 0)))
+        print('TracingAssignmentStep: %d of %d traces unassigned' % (int(np.count_nonzero(pick < 0)), T), flush=True)
+
+    def skip(self):
+        cset(self.cfg, 'runtime/tracing/assignment_file', self._path())
+
+
+def _hip_tracing(store, traces, keep_best, device):
+    from . import _lib, tracing
+    xyz = np.ascontiguousarray(store.coordinates())
+    return tracing.assign_costs(xyz, store.copy_ptr, store.copy_idx, traces, keep_best, ctx=_lib.context(device))
+
+
 KERNELS_HIP = {'damid': _hip_damid, 'nucldamid': _hip_nucldamid, 'fish': _hip_fish, 'sprite': _hip_sprite,
-               'polymer': _hip_polymer}
+               'polymer': _hip_polymer, 'tracing_assign': _hip_tracing}

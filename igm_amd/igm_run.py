@@ -5,7 +5,8 @@ up with an acceptable violation score, or max_iterations unsuccessful iterations
   start-up   starting_coordinates copied, or RandomInit [+ PolymerAssignmentStep when
              the chain is modelled by distance distributions] + RelaxInit (:50-82)
   iteration  PolymerAssignmentStep (restraints/polymer), NuclDamidActivationDistanceStep
-             (nuclDamID), ActivationDistanceStep (Hi-C), FishAssignmentStep (FISH),
+             (nuclDamID), TracingAssignmentStep (tracing with input_file),
+             ActivationDistanceStep (Hi-C), FishAssignmentStep (FISH),
              SpriteAssignmentStep (sprite), DamidActivationDistanceStep (DamID),
              ModelingStep (:105-167), in that order
   control    is_acceptable = runtime/violation_score < optimization/max_violations;
@@ -15,10 +16,12 @@ up with an acceptable violation score, or max_iterations unsuccessful iterations
 
 The nucleolus exclusion body (model/restraints/nucleolus) needs no A-step; it and
 nuclDamID are modelled on an exp_map nucleus only (ModelingStep raises otherwise, as
-the reference fails there).  Chromatin tracing (restraints/tracing) has no A-step either:
-its assignment file is an input, and the loop only works through restraints/tracing/tol_list
-as it does through the FISH one (bin/igm-run:122-133, 218-223, 283-285).  A tracing section
-without assignment_file raises: the reference has no step that could produce the file.  Preprocess (genome/index,
+the reference fails there).  Chromatin tracing (restraints/tracing) works through
+restraints/tracing/tol_list as FISH does through its own (bin/igm-run:122-133, 218-223,
+283-285).  With assignment_file the assignment is an input and there is no step, as in the
+reference; with input_file alone TracingAssignmentStep makes it from the imaged traces every
+iteration, at the place of the reference's commented-out ImagedLociAssignmentStep (:135).  A
+tracing section with neither raises: there is nothing to model.  Preprocess (genome/index,
 .hss allocation) is the caller's: the population file must exist.  No email
 notifications, no control socket.
 """
@@ -48,13 +51,17 @@ def startup_steps(cfg):
 def iteration_steps(cfg):
     """bin/igm-run:105-161"""
     R = cfg.get('restraints', {})
-    if 'tracing' in R:  # no step of its own (bin/igm-run:122-136); the file must be given
+    tr = R.get('tracing')
+    assign_traces = tr is not None and bool(tr.get('input_file')) and not tr.get('assignment_file')
+    if tr is not None and not assign_traces:  # the file is given (bin/igm-run:122-133), or nothing can be done
         ST.tracing_assignment_file(cfg)
     steps = []
     if 'polymer' in R:
         steps.append(ST.PolymerAssignmentStep)
     if 'nuclDamID' in R:  # bin/igm-run:118-119
         steps.append(ST.NuclDamidActivationDistanceStep)
+    if assign_traces:  # the place of the reference's commented-out ImagedLociAssignmentStep (bin/igm-run:135)
+        steps.append(ST.TracingAssignmentStep)
     if 'Hi-C' in R:
         steps.append(ST.ActivationDistanceStep)
     if 'FISH' in R:
@@ -85,7 +92,8 @@ def run_pipeline(cfg, on_iteration=None):
     while True:
         rt['opt_iter'] = opt_iter
         if 'tracing' in cfg.get('restraints', {}):  # bin/igm-run:122-133
-            ST.tracing_assignment_file(cfg)
+            if ST.tracing_assigned(cfg):  # (else TracingAssignmentStep makes the file in this iteration)
+                ST.tracing_assignment_file(cfg)
             tr = rt.setdefault('tracing', {})
             if 'tol_list' not in tr:
                 tr['tol_list'] = list(cfg['restraints']['tracing']['tol_list'])

@@ -15,7 +15,9 @@ loci are put at their targets and the loci between them interpolated
 (igm_amd.tracing.initial_coordinates, RandomInit.py:70-102); the model/init_noise draw, which
 the reference also takes from the unseeded global generator (D9), comes from the structure's
 own RandomState after the territories.  RelaxInit ties the traced loci to their targets with
-the fixed tolerance 50 (RelaxInit.py:186-207).
+the fixed tolerance 50 (RelaxInit.py:186-207).  Both use tracing only when an assignment file
+exists: a run on restraints/tracing/input_file alone starts as one without tracing, and its
+first assignment is made in iteration 1 (TracingAssignmentStep).
 """
 import os
 import shutil
@@ -45,7 +47,8 @@ class RandomInit(Step):
         seed = int(cget(self.cfg, 'model/init_seed', 0))
         crd = store.coordinates('r+')
         tr = None
-        if 'tracing' in (self.cfg.get('restraints') or {}):
+        from .steps import tracing_assigned
+        if tracing_assigned(self.cfg):
             from . import tracing
             from .steps import tracing_data
             tr = tracing.check_assignment(tracing_data(self.cfg), crd.shape[0])
@@ -80,7 +83,8 @@ def _hip_relax(store, sids, cfg, device):
     if rget(cfg, 'model/restraints/envelope/nucleus_shape') == 'exp_map':
         env = envelope_section(cfg, sids)
         kw = {'volumes': env['volumes'], 'volume_struct_map': env['struct_map']}
-    if 'tracing' in (cfg.get('restraints') or {}):
+    from .steps import tracing_assigned
+    if tracing_assigned(cfg):
         from .steps import tracing_data
         kw['tracing'] = tracing_data(cfg)
     return init.relax_population(cfg, batch_coordinates(store, sids), store.radii, store.chrom, store.copy, sids,

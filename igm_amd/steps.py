@@ -598,14 +598,35 @@ def modeling_spec(cfg, sids):
 
 
 def tracing_assignment_file(cfg):
-    """restraints/tracing/assignment_file; a tracing section without one cannot be modelled:
-    the reference has no assignment step that could produce the file (bin/igm-run:122-136,
-    its ImagedLociAssignmentStep is commented out)."""
-    path = (cfg.get('restraints', {}).get('tracing') or {}).get('assignment_file')
-    if not path:
-        raise NotImplementedError('restraints/tracing without assignment_file is not implemented on the hip kernel: '
-                                  'the reference has no assignment step that could produce the file')
-    return path
+    """The tracing assignment the M-step reads: runtime/tracing/assignment_file (the product of
+    TracingAssignmentStep) if set, else restraints/tracing/assignment_file (an input).  With
+    restraints/tracing/input_file alone the file does not exist before the first assignment
+    step has run (RuntimeError).  A tracing section with neither key cannot be modelled: the
+    reference has no assignment step that could produce the file (bin/igm-run:122-136, its
+    ImagedLociAssignmentStep is commented out), and ours needs the traces."""
+    path = cget(cfg, 'runtime/tracing/assignment_file', None)
+    if path:
+        return path
+    tr = cfg.get('restraints', {}).get('tracing') or {}
+    path = tr.get('assignment_file')
+    if path:
+        return path
+    if tr.get('input_file'):
+        raise RuntimeError('restraints/tracing/input_file %r has not been assigned yet: TracingAssignmentStep '
+                           'has not run (runtime/tracing/assignment_file is not set)' % tr['input_file'])
+    raise NotImplementedError('restraints/tracing without assignment_file is not implemented on the hip kernel: '
+                              'the reference has no assignment step that could produce the file')
+
+
+def tracing_assigned(cfg):
+    """True when the config's tracing data can be used now: there is an assignment file.  A
+    run on restraints/tracing/input_file alone has none before its first
+    TracingAssignmentStep; RandomInit and RelaxInit then run as without tracing."""
+    tr = (cfg.get('restraints') or {}).get('tracing')
+    if tr is None:
+        return False
+    return bool(cget(cfg, 'runtime/tracing/assignment_file', None) or tr.get('assignment_file')
+                or not tr.get('input_file'))  # (neither key: tracing_assignment_file raises)
 
 
 _TRACING = {}
@@ -803,7 +824,7 @@ class ModelingStep(Step):
 # ------------------------------------------------------------------ the other steps
 from .assign_steps import (DamidActivationDistanceStep, FishAssignmentStep,  # noqa: E402
                            NuclDamidActivationDistanceStep, PolymerAssignmentStep,
-                           SpriteAssignmentStep, KERNELS_HIP as _A_HIP)
+                           SpriteAssignmentStep, TracingAssignmentStep, KERNELS_HIP as _A_HIP)
 from .init_steps import RandomInit, RelaxInit, KERNELS_HIP as _I_HIP  # noqa: E402
 
 KERNELS['hip'].update(_A_HIP)

@@ -4,16 +4,40 @@ imaged position by a harmonic upper bound of radius `tol`.
 
 The reference adds one DUMMY_STATIC centroid per imaged locus and a bond to it; here the
 restraint is a position anchor of the engine (igm_anchor, include/igm_hip.h): no atom is
-added, so a traced 2 Mb structure stays in the LDS engine.  The reference has no A-step
-for tracing: the assignment file is an input,
+added, so a traced 2 Mb structure stays in the LDS engine.  The M-step reads the assignment
+file,
 
     locus       (n,)   diploid bead index
-    target      (n, 3) imaged position
+    target      (n, 3) imaged position in the model's frame
     assignment  (n,)   structure index the locus was imaged in
+
+which is either an input (restraints/tracing/assignment_file) or the product of the A-step
+below.  The reference has no A-step for tracing (bin/igm-run:122-136: its
+ImagedLociAssignmentStep is commented out); this one takes the traces as they are imaged
+(restraints/tracing/input_file),
+
+    trace_ptr   (T + 1,) the spots of trace t are the entries trace_ptr[t] .. trace_ptr[t + 1]
+    locus       (n,)     haploid locus of each spot, strictly increasing inside a trace, one
+                         chromosome per trace
+    position    (n, 3)   nm, in a frame of the trace's own
+
+and decides, from the current population, which (structure, copy) each trace is:
+
+  read_traces        the validated trace file
+  assign_costs       the minimal RMSD under a proper rigid motion of every (trace, structure,
+                     copy) and the keep_best cheapest candidates per trace, on the GPU
+                     (igm_tracing_assign; no CPU fallback)
+  greedy_assignment  every (structure, chromosome, copy) slot takes at most one trace: the
+                     traces in ascending order of their best cost take their first free
+                     candidate (host, deterministic)
+  aligned_targets    the assigned traces superposed on their beads (Kabsch, fp64, host)
+  write_assignment   the assignment file the M-step reads
 """
 import numpy as np
 
 from ._lib import anchor_dtype
+
+MIN_SPOTS = 3  # a rigid superposition of fewer spots says nothing
 
 
 def read_assignment(path, nbead=None):
@@ -80,3 +104,181 @@ def initial_coordinates(crd, data, sid, rng=None, init_noise=None):
         rng = np.random.mtrand._rand if rng is None else rng
         crd = crd + init_noise * rng.randn(crd.shape[0], 3)
     return crd
+
+
+# ---------------------------------------------------------------------------- the A-step
+def check_traces(data, copy_ptr, hap_chrom):
+    """The trace arrays validated against the model's index: {'trace_ptr' (T + 1,) int64,
+    'locus' (n,) int32, 'position' (n, 3) float32 -- the precision the device reads --,
+    'chrom' (T,) the chromosome of every trace, 'ncopy' (T,) its number of copies}.
+    ValueError naming the first offending trace: a non-monotone trace_ptr, fewer than
+    MIN_SPOTS spots, a locus outside [0, nhap), non-increasing loci, more than one chromosome,
+    a non-finite position."""
+    ptr = np.asarray(data['trace_ptr']).astype(np.int64).reshape(-1)
+    locus = np.asarray(data['locus']).astype(np.int64).reshape(-1)
+    position = np.asarray(data['position'], np.float64)
+    copy_ptr = np.asarray(copy_ptr, np.int64)
+    hap_chrom = np.asarray(hap_chrom)
+    nhap = len(copy_ptr) - 1
+    if len(ptr) < 1 or ptr[0] != 0:
+        raise ValueError('tracing input: trace_ptr must start at 0')
+    if position.shape != (len(locus), 3):
+        raise ValueError('tracing input: locus %r and position %r do not match' % ((len(locus),), position.shape))
+    T = len(ptr) - 1
+    d = np.diff(ptr)
+    if np.any(d < 0):
+        raise ValueError('tracing input: trace_ptr is not monotone at trace %d' % int(np.where(d < 0)[0][0]))
+    if ptr[-1] != len(locus):
+        raise ValueError('tracing input: trace_ptr ends at %d, the file has %d spots' % (ptr[-1], len(locus)))
+    if np.any(d < MIN_SPOTS):
+        t = int(np.where(d < MIN_SPOTS)[0][0])
+        raise ValueError('tracing input: trace %d has %d spots, fewer than %d' % (t, d[t], MIN_SPOTS))
+    trace = np.repeat(np.arange(T), d)
+    bad = (locus < 0) | (locus >= nhap)
+    if np.any(bad):
+        q = int(np.where(bad)[0][0])
+        raise ValueError('tracing input: trace %d: locus %d is outside [0, %d)' % (trace[q], locus[q], nhap))
+    inner = np.ones(len(locus), bool)  # spots that have a predecessor in their trace
+    inner[ptr[:-1]] = False
+    step = np.zeros(len(locus), bool)
+    step[1:] = locus[1:] <= locus[:-1]
+    if np.any(step & inner):
+        raise ValueError('tracing input: trace %d: loci are not strictly increasing' % trace[np.where(step & inner)[0][0]])
+    ch = hap_chrom[locus]
+    jump = np.zeros(len(locus), bool)
+    jump[1:] = ch[1:] != ch[:-1]
+    if np.any(jump & inner):
+        raise ValueError('tracing input: trace %d has loci of more than one chromosome' %
+                         trace[np.where(jump & inner)[0][0]])
+    fin = np.isfinite(position).all(axis=1)
+    if not np.all(fin):
+        raise ValueError('tracing input: trace %d has a non-finite position' % trace[np.where(~fin)[0][0]])
+    first = locus[ptr[:-1]]
+    return {'trace_ptr': ptr, 'locus': locus.astype(np.int32), 'position': position.astype(np.float32),
+            'chrom': np.asarray(ch[ptr[:-1]]), 'ncopy': (copy_ptr[first + 1] - copy_ptr[first]).astype(np.int32)}
+
+
+def read_traces(path, store):
+    """The trace file of restraints/tracing/input_file, validated against the population
+    `store` (copy_ptr, hap_chrom): see check_traces."""
+    from . import h5
+    with h5.File(path) as f:
+        data = {k: np.asarray(f.read(k)) for k in ('trace_ptr', 'locus', 'position')}
+    return check_traces(data, store.copy_ptr, store.hap_chrom)
+
+
+def slice_traces(traces, t0, t1):
+    """the traces t0 .. t1 as a trace set of their own"""
+    p = traces['trace_ptr']
+    return {'trace_ptr': p[t0:t1 + 1] - p[t0], 'locus': traces['locus'][p[t0]:p[t1]],
+            'position': traces['position'][p[t0]:p[t1]], 'chrom': traces['chrom'][t0:t1],
+            'ncopy': traces['ncopy'][t0:t1]}
+
+
+def assign_costs(xyz, copy_ptr, copy_idx, traces, keep_best, ctx=None, return_full=False, device=0):
+    """One igm_tracing_assign call: best_cand (T, keep_best) int32 = s * Cmax + k and best_rmsd
+    (T, keep_best) float32 in increasing order (ties to the lower candidate), Cmax = the largest
+    copy count among the traces [, and the full (T, S, Cmax) float32 matrix, +inf where k >= C_t].
+    xyz is the bead-major (nbead, S, 3) float32 population."""
+    from . import _lib
+    c = ctx or _lib.context(device)
+    xyz = np.ascontiguousarray(xyz, np.float32)
+    assert xyz.ndim == 3 and xyz.shape[2] == 3, 'xyz must be (nbead, nstruct, 3)'
+    copy_ptr = np.ascontiguousarray(copy_ptr, np.int32)
+    copy_idx = np.ascontiguousarray(copy_idx, np.int32)
+    ptr = np.ascontiguousarray(traces['trace_ptr'], np.int64)
+    locus = np.ascontiguousarray(traces['locus'], np.int32)
+    pos = np.ascontiguousarray(traces['position'], np.float32)
+    T, kb, S = len(ptr) - 1, int(keep_best), xyz.shape[1]
+    # (every locus of a trace has its trace's copy count; clipped: the library rejects a bad locus)
+    cmax = int(np.diff(copy_ptr)[np.clip(locus, 0, len(copy_ptr) - 2)].max()) if len(locus) else 1
+    bc = np.zeros((T, max(kb, 0)), np.int32)
+    bv = np.zeros((T, max(kb, 0)), np.float32)
+    full = np.zeros((T, S, cmax), np.float32) if return_full else None
+    rc = c.lib.igm_tracing_assign(c.h, 0, xyz.ctypes.data, xyz.shape[0], S, copy_ptr.ctypes.data,
+                                  copy_idx.ctypes.data, len(copy_ptr) - 1, T, ptr.ctypes.data, _lib.ptr(locus),
+                                  _lib.ptr(pos), kb, _lib.ptr(full), bc.ctypes.data, bv.ctypes.data)
+    c.check(rc, 'igm_tracing_assign')
+    return (bc, bv, full) if return_full else (bc, bv)
+
+
+def greedy_assignment(best_cand, best_rmsd, trace_chain):
+    """Which of its keep_best candidates every trace takes: pick (T,) int64, the column of
+    best_cand, -1 for a trace left unassigned.  A slot is (structure, chromosome, copy) = (the
+    candidate, trace_chain[t]: the chromosome of the trace) and takes at most one trace.  The
+    traces are visited in ascending (best_rmsd[t, 0], t); each takes its first free candidate.
+    best_cand of all traces must share one encoding (one Cmax)."""
+    best_cand = np.asarray(best_cand)
+    best_rmsd = np.asarray(best_rmsd)
+    chain = np.asarray(trace_chain)
+    T = len(best_cand)
+    pick = np.full(T, -1, np.int64)
+    taken = set()
+    for t in np.lexsort((np.arange(T), best_rmsd[:, 0])) if T else []:
+        for j, cand in enumerate(best_cand[t].tolist()):
+            slot = (cand, chain[t].item())
+            if slot not in taken:
+                taken.add(slot)
+                pick[t] = j
+                break
+    return pick
+
+
+def kabsch(p, x):
+    """(R, rmsd): the proper rotation (det = +1) and the RMSD of the best superposition
+    R (p - mean p) + mean x of the points p (n, 3) on x (n, 3), fp64."""
+    p = np.asarray(p, np.float64)
+    x = np.asarray(x, np.float64)
+    pc, xc = p - p.mean(axis=0), x - x.mean(axis=0)
+    U, sv, Vt = np.linalg.svd(xc.T @ pc)
+    d = 1.0 if np.linalg.det(U) * np.linalg.det(Vt) >= 0.0 else -1.0
+    R = U @ np.diag([1.0, 1.0, d]) @ Vt
+    r = R @ pc.T - xc.T
+    return R, float(np.sqrt(np.sum(r * r) / len(p)))
+
+
+def aligned_targets(xyz, copy_ptr, copy_idx, traces, structure, copy):
+    """The assigned traces in the model's frame.  structure / copy (T,): the slot of every
+    trace, -1 = unassigned.  Returns (target (n, 3) float64 with NaN rows for the spots of
+    unassigned traces, rmsd (T,) float64 with NaN, rotation (T, 3, 3)): Kabsch with the
+    determinant correction, target_i = R (p_i - mean p) + mean x, x the trace's beads in its
+    structure.  At most T small SVDs, so on the host."""
+    ptr = traces['trace_ptr']
+    T = len(ptr) - 1
+    target = np.full((int(ptr[-1]), 3), np.nan)
+    rmsd = np.full(T, np.nan)
+    rot = np.full((T, 3, 3), np.nan)
+    copy_ptr = np.asarray(copy_ptr, np.int64)
+    for t in range(T):
+        s, k = int(structure[t]), int(copy[t])
+        if s < 0:
+            continue
+        a, b = int(ptr[t]), int(ptr[t + 1])
+        beads = np.asarray(copy_idx)[copy_ptr[traces['locus'][a:b]] + k]
+        x = np.asarray(xyz[beads, s], np.float64)
+        p = np.asarray(traces['position'][a:b], np.float64)
+        R, rmsd[t] = kabsch(p, x)
+        rot[t] = R
+        target[a:b] = (p - p.mean(axis=0)) @ R.T + x.mean(axis=0)
+    return target, rmsd, rot
+
+
+def write_assignment(path, traces, copy_ptr, copy_idx, structure, copy, target, rmsd):
+    """The assignment file of the M-step from an A-step result: the datasets read_assignment
+    reads -- locus (the DIPLOID bead), target float64, assignment (the structure) -- over the
+    spots of the assigned traces, by trace then by spot; 'trace' (per entry) and, per trace,
+    trace_structure, trace_copy (-1 = unassigned) and trace_rmsd (NaN)."""
+    from . import h5
+    ptr = traces['trace_ptr']
+    T = len(ptr) - 1
+    structure = np.asarray(structure, np.int64)
+    copy = np.asarray(copy, np.int64)
+    trace = np.repeat(np.arange(T), np.diff(ptr))
+    keep = structure[trace] >= 0
+    copy_ptr = np.asarray(copy_ptr, np.int64)
+    slot = copy_ptr[np.asarray(traces['locus'], np.int64)[keep]] + copy[trace[keep]]
+    h5.write(path, {'locus': np.asarray(copy_idx)[slot].astype(np.int64),
+                    'target': np.ascontiguousarray(np.asarray(target, np.float64)[keep]),
+                    'assignment': structure[trace[keep]], 'trace': trace[keep].astype(np.int64),
+                    'trace_structure': structure, 'trace_copy': np.where(structure >= 0, copy, -1),
+                    'trace_rmsd': np.asarray(rmsd, np.float64)})

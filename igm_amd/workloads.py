@@ -90,6 +90,49 @@ def hic_actdist_rows(pop, sigma=0.01, contact_range=2.0):
                                  contact_range, 1)
 
 
+def random_rotation(rng):
+    """a proper rotation (det = +1), uniform over SO(3): the QR of a Gaussian matrix"""
+    q, r = np.linalg.qr(rng.normal(size=(3, 3)))
+    q = q * np.sign(np.diag(r))
+    if np.linalg.det(q) < 0:
+        q[:, 0] = -q[:, 0]
+    return q
+
+
+def synthetic_traces(store, xyz, ntrace, nspots, noise, seed):
+    """Imaged traces planted on the population xyz (nbead, S, 3) of `store` (copy_ptr, copy_idx,
+    hap_chrom as attributes or keys): trace t is a window of nspots consecutive loci of a
+    chromosome copy of one structure -- the (structure, chromosome, copy) slots all distinct --
+    under a random proper rotation, a translation of a few micrometres and Gaussian noise (nm).
+    Returns ({'trace_ptr', 'locus', 'position' float32}, planted structure (T,), planted copy
+    (T,))."""
+    get = (lambda k: store[k]) if isinstance(store, dict) else (lambda k: getattr(store, k))
+    copy_ptr, copy_idx, hap_chrom = (np.asarray(get(k)) for k in ('copy_ptr', 'copy_idx', 'hap_chrom'))
+    rng = np.random.default_rng(seed)
+    S = xyz.shape[1]
+    ncopy = np.diff(copy_ptr)
+    chroms = [c for c in np.unique(hap_chrom) if np.count_nonzero(hap_chrom == c) >= nspots]
+    slots = [(c, k) for c in chroms for k in range(int(ncopy[np.where(hap_chrom == c)[0][0]]))]
+    if ntrace > S * len(slots):
+        raise ValueError('%d traces do not fit the %d slots of %d structures' % (ntrace, S * len(slots), S))
+    take = rng.choice(S * len(slots), ntrace, replace=False)
+    ptr = np.arange(ntrace + 1, dtype=np.int64) * nspots
+    locus = np.zeros(ntrace * nspots, np.int32)
+    position = np.zeros((ntrace * nspots, 3), np.float32)
+    structure, copy = np.zeros(ntrace, np.int64), np.zeros(ntrace, np.int64)
+    for t, q in enumerate(take):
+        s, (c, k) = int(q) // len(slots), slots[int(q) % len(slots)]
+        loci = np.where(hap_chrom == c)[0]
+        w0 = int(rng.integers(0, len(loci) - nspots + 1))
+        win = loci[w0:w0 + nspots]
+        x = np.asarray(xyz[copy_idx[copy_ptr[win] + k], s], np.float64)
+        p = (x - x.mean(axis=0)) @ random_rotation(rng).T + rng.normal(0.0, 3000.0, 3) + rng.normal(0.0, noise, x.shape)
+        locus[t * nspots:(t + 1) * nspots] = win
+        position[t * nspots:(t + 1) * nspots] = p
+        structure[t], copy[t] = s, k
+    return {'trace_ptr': ptr, 'locus': locus, 'position': position}, structure, copy
+
+
 def spec_D(pop, n, scale, ctx, nlocal=15000, nlong=1500, seed=41, hic=None):
     from . import assemble as A
     from . import damid

@@ -213,6 +213,31 @@ int igm_sprite_assign(igm_ctx* ctx, uint32_t flags,
                       int32_t keep_best, float* rg2_out,
                       int32_t* best_idx, float* best_rg2, int32_t* best_sel);
 
+/* Chromatin tracing: the A-step the reference leaves open (bin/igm-run:122-136, its
+ * ImagedLociAssignmentStep is commented out).  Trace t is the imaged positions (nm, any
+ * frame) of the haploid loci locus[trace_ptr[t]..trace_ptr[t+1]) of one chromosome copy:
+ * at least 3 spots, loci strictly increasing, every locus with the same number of copies
+ * C_t.  A candidate is (structure s, copy k < C_t) with the beads
+ * x_i = xyz[copy_idx[copy_ptr[locus_i] + k], s]; its cost is the minimal RMSD under a proper
+ * rigid motion (rotation with det = +1 and translation, no reflection),
+ * sqrt(max(0, (Ga + Gb - 2 lambda) / n)) with Ga, Gb the centred sums of squares and lambda the
+ * largest eigenvalue of Horn's 4x4 key matrix, accumulated in fp64 from the f32 coordinates.
+ * Cmax is the largest C_t of the call.  Outputs: rmsd_out (ntrace, nstruct, Cmax) f32
+ * (nullable), +inf where k >= C_t; best_cand / best_rmsd (ntrace, keep_best): the keep_best
+ * smallest f32 costs of every trace in increasing order, ties to the lower candidate index
+ * s * Cmax + k.  IGM_E_INVALID: a malformed trace, keep_best < 1, keep_best larger than the
+ * smallest nstruct * C_t.  Host pointers only (the arrays are validated on the host, before
+ * any launch).  Timings: igm_last_kernel_ms "tracing_assign" (= "tracing_cost" +
+ * "tracing_select"). */
+int igm_tracing_assign(igm_ctx* ctx, uint32_t flags,
+                       const float* xyz, int32_t nbead, int32_t nstruct,
+                       const int32_t* copy_ptr, const int32_t* copy_idx, int32_t nhap,
+                       int32_t ntrace, const int64_t* trace_ptr, const int32_t* locus, const float* position,
+                       int32_t keep_best,
+                       float* rmsd_out,       /* (ntrace, nstruct, Cmax) f32 or NULL; +inf where k >= C_t */
+                       int32_t* best_cand,    /* (ntrace, keep_best): s * Cmax + k                        */
+                       float* best_rmsd);     /* (ntrace, keep_best)                                      */
+
 /* DamID lamina envelope membership (M-step restraint assembly, config D):
  * Damid._apply_envelope (igm/restraints/damid.py:112-143) for every structure at once.
  * out_flags[s, a] = base_flags[a] | (env_bit if some DamID row {loc = a, dist = d}
