@@ -1356,10 +1356,11 @@ __global__ void __launch_bounds__(NT) anneal_kernel(std::conditional_t<AN, Annea
 //   pop_force      forces, final kick, per-block kinetic-energy partial
 // The three build kernels exit at once when no structure is flagged.  Per-structure
 // sums go through per-block partials added in a fixed order, so a run is bitwise
-// reproducible.
+// reproducible.  (Retired, with their records in DESIGN.md section 4: the split sort, early
+// forces, two-level lists, the fused rebuild and the sort's phase counters.)
 constexpr int kPopBS = 256;
 constexpr int kPopSortNT = 1024;
-constexpr int kPopMaxGroups = 64;  // structure groups (streams) of one run: build counters nflag[g], nflag2[g]
+constexpr int kPopMaxGroups = 64;  // structure groups (streams) of one run: build counters nflag[g]
 #ifndef IGM_POP_CELL_CAP
 #define IGM_POP_CELL_CAP 32768
 #endif
@@ -1374,7 +1375,6 @@ constexpr int kPopMaxGroups = 64;  // structure groups (streams) of one run: bui
 // effect at protocol x0.1, had measured 49 152 0.8 % faster than 32 768.)
 constexpr int kPopCellCap = IGM_POP_CELL_CAP;
 constexpr int kPopCells = kPopCellCap + 2;  // cell offsets of a structure: real cells, non-bead run, end
-constexpr int kPopCntStride = (kPopCells + 3) & ~3;  // cell counts of a structure (16-byte rows)
 #ifndef IGM_POP_FILL_W
 #define IGM_POP_FILL_W 2
 #endif
@@ -1403,18 +1403,6 @@ constexpr int kPopRowCap = IGM_POP_ROW_CAP;
 #ifndef IGM_POP_BOND_BATCH
 #define IGM_POP_BOND_BATCH 4  // force kernel: bond entries (and partner gathers) per batch
 #endif
-#ifndef IGM_POP_FUSED
-// 1: list build + bond re-index inside the force kernel of a rebuild step.  Measured
-// on config C (protocol x0.1, same box): fused -1.8 % anneal alone, but with the
-// prefetching force kernel its 80 VGPRs spill and the pair is +2.4 %; the unfused
-// engine with the prefetch is -2 %, so 0 is the default.
-#define IGM_POP_FUSED 0
-#endif
-constexpr bool kPopFused = IGM_POP_FUSED != 0;
-#ifndef IGM_POP_OUTER_CAP
-#define IGM_POP_OUTER_CAP 80
-#endif
-constexpr int kPopOuterCap = IGM_POP_OUTER_CAP;  // outer-list entries per slot (two-level lists)
 #ifndef IGM_POP_TYPE_STAGE
 #define IGM_POP_TYPE_STAGE 512  // bond types a force block stages in LDS (4 KB); 0: always gathered
 #endif
@@ -1528,38 +1516,6 @@ struct PopArgs {
     float* bbp;          // (B, nbs, 6) per-block bounding boxes {max -x, -y, -z, max x, y, z}
     const double* dofs;  // (B) dof of group nonfixed
     int nbs;
-    // the bonds of every atom as contiguous rows (CSR, the sliced ELLPACK of prepare()
-    // re-laid out once per run): the rebuild's re-index gathers atoms in slot order,
-    // where one row is one cache line instead of one line per entry
-    const uint32_t* csr;  // entries: partner atom | type << 16 | lower << 31
-    const int* coff;      // (B, natom + 1) row offsets within the structure
-    const int64_t* cbase;  // (B) first entry of the structure
-    // Two-level lists (two != 0): the cell grid, the slot order and the OUTER list
-    // (cut_list = cut_in + the outer margin) are rebuilt only when an atom moved past
-    // half the margin since the last outer build; the inner list (cut_in, the list
-    // the force kernel reads) is re-filtered from the outer one at every other rebuild.
-    int two;
-    float cut_in;        // inner list cut (two-level), P.cut_list is then the outer one
-    float4* xo;          // (B, ldn) position of the slot at the last outer build
-    uint2* nlo;          // (B, nslice, kqo, 64) outer list quads
-    uint16_t* nnbo;      // (B, ldn) outer list length, or kNnbWalk
-    int kqo;
-    int* oflag[2];       // (B) outer margin exceeded, by step parity
-    int* flist2;         // (B) the structures whose inner list is rebuilt this step
-    int* nflag2;         // (1)
-    unsigned long long* sprof;  // optional (8): the sort kernel's phase cycles, summed (profiling)
-    // The split sort (pop_grid .. pop_rank, several 256-thread workgroups per flagged
-    // structure instead of one 1024-thread workgroup holding the grid in LDS):
-    int* ccnt;           // (B, kPopCntStride) cell counts; zero between builds (the scan clears them)
-    int* tid;            // (B, ldn) atom ids scattered into their cells (before the in-cell rank)
-    int* ctot;           // (B, 8) cells counted per scan chunk (zero between builds: the scatter clears them)
-};
-
-// one Verlet list of the engine (the inner one, or the outer one of two-level lists)
-struct PopList {
-    uint2* nl;
-    uint16_t* nnb;
-    int kq;
 };
 
 // XCD-aware block order for the kernels over every structure: the grid (padded to a
@@ -1571,38 +1527,13 @@ __device__ __forceinline__ int pop_block() {
     return (x & 7) * per + (x >> 3);
 }
 
-// CSR row offsets of every structure's bonds (one workgroup per structure): the
-// exclusive scan of the atom degrees, the structure's total at coff[natom]
-__global__ void __launch_bounds__(1024) pop_csr_scan_kernel(const int* deg, int natom, int* coff) {
-    __shared__ int wsum[1024 / 64];
-    const int s = blockIdx.x;
-    block_scan<1024, int, int>(deg + (size_t)s * natom, coff + (size_t)s * (natom + 1), natom, wsum);
-}
-
-// the entries of every atom's row from the sliced ELLPACK adjacency
-__global__ void __launch_bounds__(256) pop_csr_fill_kernel(Bonds Bd, int nstruct, int natom, int nslice,
-                                                            const int* coff, const int64_t* cbase, uint32_t* csr) {
-    const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (x >= (int64_t)nstruct * natom) return;
-    const int s = (int)(x / natom), a = (int)(x - (int64_t)s * natom);
-    const int deg = Bd.deg[x];
-    const uint32_t* g = Bd.ent + Bd.base[s] + Bd.soff[(size_t)s * (nslice + 1) + (a >> 6)] + (a & 63);
-    uint32_t* o = csr + cbase[s] + coff[(size_t)s * (natom + 1) + a];
-    for (int e = 0; e < deg; ++e) o[e] = g[(size_t)e * 64];
-}
-
 __global__ void __launch_bounds__(kPopBS) pop_load_kernel(PopArgs A, const float* xyz) {
     const int lb = pop_block(), s = lb / A.nbs, a = (lb % A.nbs) * kPopBS + threadIdx.x;
     if (s >= A.cm.nstruct) return;
-    if (lb == 0 && threadIdx.x == 0) {
-        *A.nflag = 0;
-        if (A.two) *A.nflag2 = 0;
-    }
+    if (lb == 0 && threadIdx.x == 0) *A.nflag = 0;
     if (a == 0) {
         A.flag[0][s] = 1;  // the first step builds
         A.flag[1][s] = 0;
-        A.oflag[0][s] = 1;
-        A.oflag[1][s] = 0;
         A.nrebuild[s] = 0;
         A.par[s] = 0;
     }
@@ -1628,7 +1559,6 @@ __global__ void __launch_bounds__(kPopBS) pop_load_kernel(PopArgs A, const float
     B.slot[i] = a;
     const float inf = __int_as_float(0x7f800000);
     A.xb[i] = pop_f3{inf, inf, inf};
-    if (A.two) A.xo[i] = make_float4(inf, inf, inf, 0.f);
 }
 
 // velocities of a run: 'velocity create' of segment seg (vsrc = vinit + seg stride) or
@@ -1644,13 +1574,11 @@ __global__ void __launch_bounds__(kPopBS) pop_setvel_kernel(PopArgs A, const flo
 
 struct PopStep {
     float dtv, dtf, vlim, vlimsq, trig;
-    float trig_out;   // two-level lists: (outer margin / 2)^2
     int integrate;    // 0: neighbour check only (run setup)
     int rescale;      // apply the temp/rescale of step `prev` first
     int prev, nsteps;
     float t0, t1, window, fraction;
     int fp;           // parity of this step's rebuild flags
-    int part;         // force kernel: 0 every structure, 1 those not rebuilt this step, 2 those rebuilt
 };
 
 // temp/rescale factor of structure s at the end of step P.prev (fixed-order sum of partials)
@@ -1685,9 +1613,8 @@ __global__ void __launch_bounds__(kPopBS) pop_integrate_kernel(PopArgs A, PopSte
     const uint32_t fl = B.flg[k];
     const pop_f3 f = B.frc[k];
     const pop_f3 b = A.xb[k];
-    const float4 bo = A.two ? A.xo[k] : make_float4(b.x, b.y, b.z, 0.f);
     const float factor = S.rescale ? pop_factor(A, S, s, &fac) : 1.0f;
-    int moved = 0, moved_o = 0;
+    int moved = 0;
     float mm[6] = {-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f};
     if (live) {
         if (S.integrate && !(fl & IGM_ATOM_FIXED)) {
@@ -1708,8 +1635,6 @@ __global__ void __launch_bounds__(kPopBS) pop_integrate_kernel(PopArgs A, PopSte
         if (p.w >= 0.0f) {
             const float dx = p.x - b.x, dy = p.y - b.y, dz = p.z - b.z;
             moved = !(dx * dx + dy * dy + dz * dz <= S.trig);
-            const float ox = p.x - bo.x, oy = p.y - bo.y, oz = p.z - bo.z;
-            moved_o = !(ox * ox + oy * oy + oz * oz <= S.trig_out);
             mm[0] = -p.x;
             mm[1] = -p.y;
             mm[2] = -p.z;
@@ -1726,7 +1651,6 @@ __global__ void __launch_bounds__(kPopBS) pop_integrate_kernel(PopArgs A, PopSte
 #pragma unroll
         for (int d = 0; d < 6; ++d) red[(threadIdx.x >> 6) * 6 + d] = mm[d];
     if (__syncthreads_or(moved) && threadIdx.x == 0) atomicOr(&A.flag[S.fp][s], 1);
-    if (A.two && __syncthreads_or(moved_o) && threadIdx.x == 0) atomicOr(&A.oflag[S.fp][s], 1);
     if (threadIdx.x < 6) {
         float m = red[threadIdx.x];
 #pragma unroll
@@ -1740,8 +1664,7 @@ __global__ void __launch_bounds__(kPopBS) pop_integrate_kernel(PopArgs A, PopSte
 // order is x-fastest, so an x run of cells stays one slot range, and a slot's list build
 // visits only the x cells its cut_list sphere meets in each row), at most A.ccap cells.
 // Stored to gp (lo[3], inv[3]) and gn (nb[3], x reach); sg/sn get lo, inv and nb.
-__device__ __forceinline__ void pop_grid_of(const PopArgs& A, int s, const float (&mm)[6], float* sg, int* sn,
-                                            bool store = true) {
+__device__ __forceinline__ void pop_grid_of(const PopArgs& A, int s, const float (&mm)[6], float* sg, int* sn) {
     float ext[3], vol = 1.0f;
     const float cut = A.P.cut_list;
 #pragma unroll
@@ -1768,18 +1691,16 @@ __device__ __forceinline__ void pop_grid_of(const PopArgs& A, int s, const float
         nbv[2] = g.z;
     }
     // x cells a pair within cut_list can be apart (the cell walk's x reach)
-    if (store) gn[3] = ext[0] > 0.0f ? max(1, (int)ceilf(cut * (float)nbv[0] / ext[0] * 1.00001f)) : 1;
+    gn[3] = ext[0] > 0.0f ? max(1, (int)ceilf(cut * (float)nbv[0] / ext[0] * 1.00001f)) : 1;
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
         const int nbd = nbv[d];
         sg[d] = -mm[d];
         sg[3 + d] = ext[d] > 0.0f ? (float)nbd / ext[d] : 0.0f;
         sn[d] = nbd;
-        if (store) {
-            gp[d] = sg[d];
-            gp[3 + d] = sg[3 + d];
-            gn[d] = nbd;
-        }
+        gp[d] = sg[d];
+        gp[3 + d] = sg[3 + d];
+        gn[d] = nbd;
     }
 }
 
@@ -1794,9 +1715,6 @@ __device__ __forceinline__ void pop_grid_of(const PopArgs& A, int s, const float
 // N <= APT * kPopSortNT) in registers, and all their loads are in flight together --
 // the sort is one workgroup's chain of dependent memory round trips, so fewer and
 // wider trips are what makes it faster.
-#ifndef IGM_POP_SORT_PROF
-#define IGM_POP_SORT_PROF 0  // 1: per-phase cycle counters of the sort (with IGM_POP_SORT_PROF set at run time)
-#endif
 template <bool IDS_LDS, int APT>
 __global__ void __launch_bounds__(kPopSortNT) pop_sort_kernel(PopArgs A, int fp) {
     extern __shared__ __attribute__((aligned(16))) uint32_t cw[];  // (kPopCells + 1) / 2 words, then ids
@@ -1805,22 +1723,6 @@ __global__ void __launch_bounds__(kPopSortNT) pop_sort_kernel(PopArgs A, int fp)
     __shared__ int sn[3];
     const int s = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
     if (!A.flag[fp][s]) return;
-#if IGM_POP_SORT_PROF
-    unsigned long long tp = A.sprof ? clock64() : 0;
-    auto phase = [&](int k) {  // profiling builds: thread 0 charges the cycles since the last mark
-        if (A.sprof && t == 0) {
-            const unsigned long long now = clock64();
-            atomicAdd(&A.sprof[k], now - tp);
-            tp = now;
-        }
-    };
-#else
-    auto phase = [](int) {};
-#endif
-    if (A.two) {  // every rebuild re-filters the inner list; the outer one waits for its margin
-        if (t == 0) A.flist2[atomicAdd(A.nflag2, 1)] = s;
-        if (!A.oflag[fp][s]) return;
-    }
     const int N = A.cm.natom;
     const size_t base = (size_t)s * A.cm.ldn;
     const int p = A.par[s], q = p ^ 1;
@@ -1852,7 +1754,6 @@ __global__ void __launch_bounds__(kPopSortNT) pop_sort_kernel(PopArgs A, int fp)
     uint16_t* ids = reinterpret_cast<uint16_t*>(cw + ((A.ccap + 3) >> 1));
     for (int k = t; k < nw; k += kPopSortNT) cw[k] = 0u;
     __syncthreads();
-    phase(0);  // grid from the bbox partials, counts cleared
     constexpr int U = 4;  // independent loads in flight per thread
     uint32_t cr[APT > 0 ? APT : 1];
     if constexpr (APT > 0) {
@@ -1894,7 +1795,6 @@ __global__ void __launch_bounds__(kPopSortNT) pop_sort_kernel(PopArgs A, int fp)
         }
     }
     __syncthreads();
-    phase(1);  // positions loaded, cells counted
     // exclusive scan of the u16 counts in place (offsets <= N < 65536 fit the halves)
     {
         const int cpt = (nw + kPopSortNT - 1) / kPopSortNT, k0 = t * cpt;
@@ -1917,7 +1817,6 @@ __global__ void __launch_bounds__(kPopSortNT) pop_sort_kernel(PopArgs A, int fp)
         }
     }
     __syncthreads();
-    phase(2);  // scan
     auto off = [&](int c) -> int { return (int)((cw[c >> 1] >> ((c & 1) << 4)) & 0xffffu); };
     auto put = [&](int k, int v) {
         if (IDS_LDS)
@@ -1955,12 +1854,11 @@ __global__ void __launch_bounds__(kPopSortNT) pop_sort_kernel(PopArgs A, int fp)
             if (i0 + u * kPopSortNT < N) put(off((int)(uu[u] >> 16)) + (int)(uu[u] & 0xffffu), aa[u]);
     }
     __syncthreads();
-    phase(3);  // ids scattered into their cells
     if constexpr (APT > 0) {
         // deterministic order inside a cell: an atom's slot is its cell's first slot plus
         // the number of the cell's atoms with a smaller id (independent LDS reads per
-        // atom, where an insertion sort per cell is a serial chain of them).  (Measured,
-        // IGM_POP_SORT_PROF: this phase is ~half of the kernel; keeping slot and id in
+        // atom, where an insertion sort per cell is a serial chain of them).  (Measured with
+        // per-phase cycle counters: this phase is ~half of the kernel; keeping slot and id in
         // registers for coalesced stores after a barrier was 2.5 % slower on the anneal.)
 #pragma unroll
         for (int u = 0; u < APT; ++u) {
@@ -1998,17 +1896,9 @@ __global__ void __launch_bounds__(kPopSortNT) pop_sort_kernel(PopArgs A, int fp)
             A.inv[base + i] = o;
         }
     }
-    phase(4);  // ranks inside the cells, new slot order stored
     int* cg = A.cell + (size_t)s * kPopCells;
     for (int c = t; c <= ncell + 1; c += kPopSortNT) cg[c] = off(c);
     if (t == 0) A.par[s] = q;
-#if IGM_POP_SORT_PROF
-    if (A.sprof) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (profiling: this wave's stores done)
-        phase(5);  // cell offsets stored
-        if (t == 0) atomicAdd(&A.sprof[6], 1ull);
-    }
-#endif
 }
 
 // LDS bytes of pop_sort_kernel<IDS_LDS> over grids of at most ccap cells
@@ -2026,174 +1916,14 @@ inline int pop_sort_cells(int natom) {
 }
 static_assert(kPopCells < 65536, "cell ids are packed in 16 bits");
 
-// ---- The split sort: the same slot order as pop_sort_kernel (same grid, same cells, ids
-// ascending inside a cell), built by several workgroups per flagged structure with the
-// counts and ids in HBM/L2 instead of one CU's LDS (pop_sort_kernel holds 124 KB of LDS
-// for ~200 us per flagged structure, which keeps the other structure group's kernels off
-// that CU, profiles/r05_ab).
-//   pop_count    every slot of every flagged structure: the grid (each block from the bbox
-//                partials; block 0 stores it and the flist entry), the slot's cell, its
-//                arrival rank there (global atomic), key = c << 16 | rank; chunk totals
-//   pop_scan     per flagged structure and chunk of kScanChunk cells: cell offsets
-//                (exclusive scan from the chunk totals before it), counts cleared, parity flipped
-//   pop_scatter  per slot: its atom id at its cell's first slot + arrival rank
-//   pop_rank     per slot: new slot = cell's first slot + ids of the cell below its own
-// The arrival ranks differ run to run; the in-cell order (ascending ids) does not.
-// The kernels after pop_count run a grid of `per` structure slots x nbs blocks, and block
-// b takes flagged structures b / nbs, + per, ... (*nflag of them).
-constexpr int kScanLog = 13, kScanChunk = 1 << kScanLog, kScanChunks = 8;  // 8 x 8192 >= kPopCells
-static_assert(kScanChunk * kScanChunks >= kPopCells, "the scan chunks cover every cell");
-
-__global__ void __launch_bounds__(kPopBS) pop_count_kernel(PopArgs A, int fp) {
-    __shared__ float sgl[6];
-    __shared__ int snb[3], scc[kScanChunks];
-    const int s = blockIdx.x / A.nbs, blk = blockIdx.x % A.nbs, t = threadIdx.x, i = blk * kPopBS + t;
-    if (s >= A.cm.nstruct || !A.flag[fp][s]) return;  // (block-uniform)
-    if (t < kScanChunks) scc[t] = 0;
-    if (t < 64) {  // the structure's bead bbox from the blocks' partials (max: exact in any order)
-        const float* bp = A.bbp + (size_t)s * A.nbs * 6;
-        float mm[6];
-#pragma unroll
-        for (int d = 0; d < 6; ++d) mm[d] = -3.0e38f;
-        for (int b = t; b < A.nbs; b += 64)
-#pragma unroll
-            for (int d = 0; d < 6; ++d) mm[d] = fmaxf(mm[d], bp[b * 6 + d]);
-#pragma unroll
-        for (int d = 0; d < 6; ++d) mm[d] = wave_max_f32(mm[d]);
-        if (t == 0) {
-            float sg[6];
-            int sn[3];
-            pop_grid_of(A, s, mm, sg, sn, blk == 0);
-            if (blk == 0) A.flist[atomicAdd(A.nflag, 1)] = s;
-#pragma unroll
-            for (int d = 0; d < 6; ++d) sgl[d] = sg[d];
-#pragma unroll
-            for (int d = 0; d < 3; ++d) snb[d] = sn[d];
-        }
-    }
-    __syncthreads();
-    if (i < A.cm.natom) {
-        const float lo[3] = {sgl[0], sgl[1], sgl[2]}, inv[3] = {sgl[3], sgl[4], sgl[5]};
-        const int nb[3] = {snb[0], snb[1], snb[2]};
-        const size_t base = (size_t)s * A.cm.ldn;
-        const float4 p = A.buf[A.par[s]].pos[base + i];
-        const int c = p.w >= 0.0f ? pop_cell_index(p.x, p.y, p.z, lo, inv, nb) : pop_ncell(nb);
-        const int r = atomicAdd(A.ccnt + (size_t)s * kPopCntStride + c, 1);
-        atomicAdd(&scc[c >> kScanLog], 1);  // (the chunk totals: one global add per block and chunk,
-        A.remap[base + i] = (c << 16) | r;   // not per slot -- a few words take every slot's add)
-    }
-    __syncthreads();
-    if (t < kScanChunks && scc[t]) atomicAdd(A.ctot + (size_t)s * kScanChunks + t, scc[t]);
-}
-
-// exclusive scan of the counts of cells 0..ncell (the last one the non-bead run) into the
-// cell offsets (cell[ncell + 1] = N): one workgroup per (flagged structure, chunk of
-// kScanChunk cells), 8 cells per thread, the chunk's base from the chunk totals before it;
-// the counts cleared behind
-template <int NT>
-__global__ void __launch_bounds__(NT) pop_scan_kernel(PopArgs A) {
-    static_assert(8 * NT == kScanChunk, "one tile per chunk");
-    __shared__ int wsum[NT / 64];
-    const int nf = *A.nflag, t = threadIdx.x, lane = t & 63, w = t >> 6, ch = blockIdx.x % kScanChunks;
-    for (int k = blockIdx.x / kScanChunks; k < nf; k += gridDim.x / kScanChunks) {
-        const int s = A.flist[k];
-        const int* gn = A.gn + (size_t)s * 8;
-        const int n = gn[0] * gn[1] * gn[2] + 1;  // cells and the non-bead run
-        const int c0 = ch * kScanChunk;
-        if (c0 >= n) continue;  // (block-uniform)
-        const int* ct = A.ctot + (size_t)s * kScanChunks;
-        int run = 0;
-        for (int q = 0; q < ch; ++q) run += ct[q];
-        int4* cnt = reinterpret_cast<int4*>(A.ccnt + (size_t)s * kPopCntStride);
-        int* cg = A.cell + (size_t)s * kPopCells;
-        const int c = c0 + 8 * t;
-        int4 a = make_int4(0, 0, 0, 0), b = make_int4(0, 0, 0, 0);
-        if (c < n) {  // (the stride rounds the rows to 4: c + 4 < kPopCntStride)
-            a = cnt[c >> 2];
-            b = c + 4 < n ? cnt[(c >> 2) + 1] : make_int4(0, 0, 0, 0);
-        }
-        const int v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-        int sum = 0;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) sum += v[u];
-        int incl = sum;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int y = __shfl_up(incl, off);
-            if (lane >= off) incl += y;
-        }
-        if (lane == 63) wsum[w] = incl;
-        __syncthreads();
-        int ex = run + incl - sum, tile = 0;
-        for (int q = 0; q < NT / 64; ++q) {
-            ex += q < w ? wsum[q] : 0;
-            tile += wsum[q];
-        }
-        if (c < n) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                if (c + u < n) cg[c + u] = ex;
-                ex += v[u];
-            }
-            const int4 z = make_int4(0, 0, 0, 0);
-            cnt[c >> 2] = z;
-            if (c + 4 < n) cnt[(c >> 2) + 1] = z;
-        }
-        if (t == 0) {
-            if (c0 + kScanChunk >= n) cg[n] = run + tile;  // = N (the chunk holding the last cell)
-            if (ch == 0) A.par[s] ^= 1;  // the slot order being built is the other buffer's
-        }
-        __syncthreads();  // (wsum reused by the next structure)
-    }
-}
-
-__global__ void __launch_bounds__(kPopBS) pop_scatter_kernel(PopArgs A) {
-    const int nf = *A.nflag, per = gridDim.x / A.nbs, i = (blockIdx.x % A.nbs) * kPopBS + threadIdx.x;
-    if (i >= A.cm.natom) return;
-    for (int k = blockIdx.x / A.nbs; k < nf; k += per) {
-        const int s = A.flist[k];
-        if (i < kScanChunks) A.ctot[(size_t)s * kScanChunks + i] = 0;  // (read by the scan launch before)
-        const size_t base = (size_t)s * A.cm.ldn;
-        const uint32_t key = (uint32_t)A.remap[base + i];
-        const int* cg = A.cell + (size_t)s * kPopCells;
-        A.tid[base + cg[key >> 16] + (key & 0xffffu)] = A.buf[A.par[s] ^ 1].aid[base + i];
-    }
-}
-
-__global__ void __launch_bounds__(kPopBS) pop_rank_kernel(PopArgs A) {
-    const int nf = *A.nflag, per = gridDim.x / A.nbs, i = (blockIdx.x % A.nbs) * kPopBS + threadIdx.x;
-    if (i >= A.cm.natom) return;
-    for (int k = blockIdx.x / A.nbs; k < nf; k += per) {
-        const int s = A.flist[k];
-        const size_t base = (size_t)s * A.cm.ldn;
-        const uint32_t key = (uint32_t)A.remap[base + i];
-        const int c = (int)(key >> 16);
-        const int* cg = A.cell + (size_t)s * kPopCells;
-        const int beg = cg[c], end = cg[c + 1];
-        const int q = A.par[s], a = A.buf[q ^ 1].aid[base + i];
-        const int* id = A.tid + base;
-        int r = 0;
-        for (int j = beg; j < end; ++j) r += id[j] < a ? 1 : 0;
-        const int n = beg + r;
-        A.buf[q].aid[base + n] = a;
-        A.buf[q].slot[base + a] = n;
-        A.remap[base + i] = n;  // (old slot i -> new slot)
-        A.inv[base + n] = i;
-    }
-}
-
-// state (and with BONDS the bonds; the fused force kernel re-indexes them itself) of
-// every slot of a flagged structure into its new slot order: block b works on flagged
-// structure b / nbs (plain order: the working blocks are dealt over all XCDs)
-template <bool BONDS>
+// state and bonds of every slot of a flagged structure into its new slot order: block b
+// works on flagged structure b / nbs (plain order: the working blocks are dealt over all XCDs)
 __device__ __forceinline__ void pop_permute_slot(const PopArgs& A, int s, int i);
-template <bool BONDS>
 __global__ void __launch_bounds__(kPopBS) pop_permute_kernel(PopArgs A) {
     const int k = blockIdx.x / A.nbs, i = (blockIdx.x % A.nbs) * kPopBS + threadIdx.x;
     if (k >= *A.nflag || i >= A.cm.natom) return;  // (idle blocks: the structure was not flagged)
-    pop_permute_slot<BONDS>(A, A.flist[k], i);
+    pop_permute_slot(A, A.flist[k], i);
 }
-template <bool BONDS>
 __device__ __forceinline__ void pop_permute_slot(const PopArgs& A, int s, int i) {
     const size_t base = (size_t)s * A.cm.ldn, k = base + i;
     const int q = A.par[s], p = q ^ 1;
@@ -2205,8 +1935,6 @@ __device__ __forceinline__ void pop_permute_slot(const PopArgs& A, int s, int i)
     B.flg[k] = O.flg[base + o];
     // (no force: the force kernel of this step rewrites every slot's before any read)
     A.xb[k] = pop_f3{x.x, x.y, x.z};
-    if (A.two) A.xo[k] = make_float4(x.x, x.y, x.z, 0.f);
-    if (!BONDS) return;
     // the old slot's bonds, partners re-indexed old slot -> new slot
     const int nsl = A.cm.nslice;
     const int deg = A.bdegb[p][base + o];
@@ -2291,20 +2019,18 @@ __device__ __forceinline__ float4 pop_ld(__amdgpu_buffer_rsrc_t r, uint32_t j) {
 
 // The Verlet list of bead slot i of structure s (p0 its position): collected in the
 // thread's LDS row `row` (kPopListRow u16), padded to whole quads with the slot itself,
-// stored as quads to the global list and its length (or kNnbWalk) to nnb.  Returns
-// the number of entries (> kcap: the slot takes its pairs from the cell walk).
-//   FLUSH: the row (rowcap entries) is stored and emptied whenever it holds flush_at
-// entries, so the list may be longer than the row (the fused force kernel reads its
-// list from the row: no flush, the list capacity capped at the row's).
-template <bool FLUSH>
-__device__ __forceinline__ int pop_fill_slot(const PopArgs& A, const PopList& T, int s, int i, size_t base,
-                                             const float4* pos, float4 p0, uint32_t* row, int rowcap) {
+// stored as quads to the global list and its length to nnb (kNnbWalk past kcap entries:
+// the slot takes its pairs from the cell walk).
+//   The row (rowcap entries) is stored and emptied whenever it holds flush_at entries, so
+// the list may be longer than the row.
+__device__ __forceinline__ void pop_fill_slot(const PopArgs& A, int s, int i, size_t base, const float4* pos,
+                                             float4 p0, uint32_t* row, int rowcap) {
     const float* gp = A.gp + (size_t)s * 8;
     const int* gn = A.gn + (size_t)s * 8;
     const int* cell = A.cell + (size_t)s * kPopCells;
-    const int kcap = FLUSH ? 4 * T.kq : min(4 * T.kq, rowcap & ~3);
+    const int kcap = 4 * A.kq;
     uint16_t* lst = reinterpret_cast<uint16_t*>(row);
-    uint64_t* out = reinterpret_cast<uint64_t*>(T.nl + ((size_t)s * A.cm.nslice + (i >> 6)) * T.kq * 64 + (i & 63));
+    uint64_t* out = reinterpret_cast<uint64_t*>(A.nl + ((size_t)s * A.cm.nslice + (i >> 6)) * A.kq * 64 + (i & 63));
     const float cut2 = A.P.cut_list * A.P.cut_list;
     // k: entries found; kr: entries in the row; qo: quads stored.  A flush check follows
     // every group of at most 8 tests, so the row never holds more than flush_at + 7.
@@ -2312,7 +2038,7 @@ __device__ __forceinline__ int pop_fill_slot(const PopArgs& A, const PopList& T,
     const int flush_at = (rowcap - 8) & ~3;
     int k = 0, kr = 0, qo = 0;
     auto flush = [&]() {
-        if (FLUSH && kr >= flush_at) {
+        if (kr >= flush_at) {
 #pragma unroll 1
             for (int q = 0; q < (flush_at >> 2); ++q)
                 out[(size_t)(qo + q) * 64] = ((uint64_t)row[2 * q + 1] << 32) | row[2 * q];
@@ -2380,11 +2106,10 @@ __device__ __forceinline__ int pop_fill_slot(const PopArgs& A, const PopList& T,
         for (int q = 0; q < (kr + 3) >> 2; ++q)
             out[(size_t)(qo + q) * 64] = ((uint64_t)row[2 * q + 1] << 32) | row[2 * q];
     }
-    T.nnb[base + i] = (uint16_t)(k <= kcap ? k : kNnbWalk);
-    return k;
+    A.nnb[base + i] = (uint16_t)(k <= kcap ? k : kNnbWalk);
 }
 
-// Verlet list of every bead slot of a flagged structure (the unfused engine): the 27
+// Verlet list of every bead slot of a flagged structure: the 27
 // cells around its cell, each x-run of cells one contiguous slot range.  Measured on
 // config C (kernel traces, scripts/gpu_profab.sh): collecting the list in an LDS row
 // and storing it a quad at a time is 13 % faster than one global u16 store per entry;
@@ -2395,9 +2120,8 @@ __device__ __forceinline__ int pop_fill_slot(const PopArgs& A, const PopList& T,
 //   One block per (flagged structure, slot block): the grid covers every structure of the
 // group and the blocks past *nflag exit (a loop over the flagged structures in a smaller grid
 // costs the kernel 8 VGPRs: 74, 6 waves per SIMD instead of 7, profiles/r06_ab).
-template <int ROW>
 __global__ void __launch_bounds__(kPopBS) pop_fill_kernel(PopArgs A) {
-    __shared__ uint32_t lrow[kPopBS * ROW / 2];
+    __shared__ uint32_t lrow[kPopBS * kPopListRow / 2];
     const int kb = blockIdx.x / A.nbs;
     if (kb >= *A.nflag) return;  // an idle block (the structure was not flagged)
     const int s = A.flist[kb], blk = blockIdx.x % A.nbs, t = threadIdx.x, i = blk * kPopBS + t;
@@ -2405,72 +2129,10 @@ __global__ void __launch_bounds__(kPopBS) pop_fill_kernel(PopArgs A) {
     const float4* pos = A.buf[A.par[s]].pos + base;
     if (i >= A.cm.natom) return;
     const float4 p0 = pos[i];
-    const PopList T = A.two ? PopList{A.nlo, A.nnbo, A.kqo} : PopList{A.nl, A.nnb, A.kq};
     if (p0.w >= 0.0f)
-        pop_fill_slot<true>(A, T, s, i, base, pos, p0, lrow + t * (ROW / 2), ROW - 2);
+        pop_fill_slot(A, s, i, base, pos, p0, lrow + t * (kPopListRow / 2), kPopListRow - 2);
     else
-        T.nnb[base + i] = 0;
-}
-
-// Two-level lists: the inner Verlet list (cut_in) of every slot of a structure whose
-// inner list is rebuilt this step, filtered from its outer list (no cell walk, no new
-// slot order); a slot whose outer list overflowed keeps the cell walk.  Same output
-// format as pop_fill_slot (quads of slot ids in the list's order, the last one padded
-// with the slot itself).
-__global__ void __launch_bounds__(kPopBS) pop_refilter_kernel(PopArgs A) {
-    __shared__ uint32_t lrow[kPopBS * kPopListRow / 2];
-    const int kb = blockIdx.x / A.nbs;
-    if (kb >= *A.nflag2) return;
-    const int s = A.flist2[kb], t = threadIdx.x, i = (blockIdx.x % A.nbs) * kPopBS + t;
-    if (i >= A.cm.natom) return;
-    const size_t base = (size_t)s * A.cm.ldn;
-    const float4* pos = A.buf[A.par[s]].pos + base;
-    const float4 p0 = pos[i];
-    A.xb[base + i] = pop_f3{p0.x, p0.y, p0.z};  // the inner build position
-    if (!(p0.w >= 0.0f)) {
         A.nnb[base + i] = 0;
-        return;
-    }
-    const int no = A.nnbo[base + i];
-    if (no == kNnbWalk) {
-        A.nnb[base + i] = kNnbWalk;
-        return;
-    }
-    uint32_t* row = lrow + t * (kPopListRow / 2);
-    uint16_t* lst = reinterpret_cast<uint16_t*>(row);
-    const int kcap = min(4 * A.kq, kPopRowCap & ~3);  // (the list collects in the LDS row)
-    const float cut2 = A.cut_in * A.cut_in;
-    const __amdgpu_buffer_rsrc_t rp = pop_rsrc(pos, A.cm.natom);
-    const uint2* go = A.nlo + ((size_t)s * A.cm.nslice + (i >> 6)) * A.kqo * 64 + (i & 63);
-    int k = 0;
-    auto test = [&](uint32_t j) {
-        const float3 p = pop_ld3(rp, j);
-        const float dx = p0.x - p.x, dy = p0.y - p.y, dz = p0.z - p.z;
-        const bool in = j != (uint32_t)i && dx * dx + dy * dy + dz * dz < cut2;  // (the padding is the slot)
-        if (in && k < kcap) lst[k] = (uint16_t)j;
-        k += in ? 1 : 0;
-    };
-    const int nq = (no + 3) >> 2;
-    for (int q0 = 0; q0 < nq; q0 += 2) {  // two quads (8 candidates) in flight
-        const uint2 e0 = go[(size_t)q0 * 64];
-        const uint2 e1 = q0 + 1 < nq ? go[(size_t)(q0 + 1) * 64] : make_uint2(i * 0x10001u, i * 0x10001u);
-        test(e0.x & 0xffffu);
-        test(e0.x >> 16);
-        test(e0.y & 0xffffu);
-        test(e0.y >> 16);
-        test(e1.x & 0xffffu);
-        test(e1.x >> 16);
-        test(e1.y & 0xffffu);
-        test(e1.y >> 16);
-    }
-    for (int kk = k; kk < kcap && (kk & 3); ++kk) lst[kk] = (uint16_t)i;
-    const int nlist = k <= kcap ? ((k + 3) & ~3) : 0;
-    if (nlist > 0) {
-        uint64_t* out = reinterpret_cast<uint64_t*>(A.nl + ((size_t)s * A.cm.nslice + (i >> 6)) * A.kq * 64 + (i & 63));
-#pragma unroll 1
-        for (int q = 0; q < nlist >> 2; ++q) out[(size_t)q * 64] = ((uint64_t)row[2 * q + 1] << 32) | row[2 * q];
-    }
-    A.nnb[base + i] = (uint16_t)(k <= kcap ? k : kNnbWalk);
 }
 
 // pair forces of a slot past the Verlet-list capacity: the 27 cells of the build-time
@@ -2511,18 +2173,13 @@ __device__ __noinline__ float4 pop_walk_pairs(const float4* pos, const int* cell
 // place of the IEEE sqrt/divide expansions, no calls (a call would put the kernel
 // arguments in scratch).  Neighbours and bond partners are loaded a batch at a time
 // so their gathers are in flight together; a masked tail keeps the batch branch-free.
-//   Fused rebuild step (lrow != null): the slot's list was just built into its LDS row
-// (nn_built entries) and is read from there; the slot's bonds are re-indexed from the
-// atom-space adjacency into the new slot order here (written to bent/bdeg for the
-// following steps) and used directly.
 //   AN: the position anchors of the slot's ATOM (aid of the slot: anchors belong to atom
 // ids, whatever the slot order), added after the bonds.
 template <bool AN>
 __device__ __forceinline__ void pop_slot_force(const PopArgs& A, int s, int i, size_t base, const float4* pos,
                                                uint32_t fl, float evf, float envf, float& fx, float& fy,
                                                float& fz, const IGM_LDS float2* sbt, bool lds_types,
-                                               const AnchorsDev An, const uint32_t* lrow = nullptr,
-                                               int nn_built = 0) {
+                                               const AnchorsDev An) {
     constexpr int U = kPopPairBatch;  // list quads per batch
     const int nsl = A.cm.nslice;
     const uint2* gl = A.nl + ((size_t)s * nsl + (i >> 6)) * A.kq * 64 + (i & 63);
@@ -2535,33 +2192,17 @@ __device__ __forceinline__ void pop_slot_force(const PopArgs& A, int s, int i, s
     const float xi = p0.x, yi = p0.y, zi = p0.z, ri = p0.w;
     fx = fy = fz = 0.0f;
     const float evfpi = evf * 0.318309886183790671537767526745f;
-    const bool rebuilt = lrow != nullptr;
-    const int nn = rebuilt ? (nn_built <= min(4 * A.kq, (kPopListRow - 2) & ~3) ? nn_built : kNnbWalk)
-                           : A.nnb[base + i];
-    const int* sl = A.buf[A.par[s]].slot + base;
-    int a_id = 0;
-    const uint32_t* ga = nullptr;  // atom-space adjacency (rebuilt step)
-    int deg;
-    if (rebuilt) {
-        a_id = A.buf[A.par[s]].aid[base + i];
-        const int* co = A.coff + (size_t)s * (A.cm.natom + 1);
-        const int r0 = co[a_id];
-        deg = co[a_id + 1] - r0;
-        ga = A.csr + A.cbase[s] + r0;
-        A.bdegb[A.par[s]][base + i] = (uint16_t)deg;
-    } else {
-        deg = pruned ? A.bcn[base + i] : A.bdegb[A.par[s]][base + i];
-    }
+    const int nn = A.nnb[base + i];
+    const int deg = pruned ? A.bcn[base + i] : A.bdegb[A.par[s]][base + i];
 #if IGM_POP_PREFETCH
     // Latency: the slot's loads, its first list quad and first bond entries go out in
     // one memory round trip (their addresses depend on (s, i) only; slots past the
     // atom's own are clamped into the allocated region and never used).
-    uint2 qnext = make_uint2(i * 0x10001u, i * 0x10001u);
-    if (!rebuilt) qnext = gl[0];
+    const uint2 qnext = gl[0];
     constexpr int UB = IGM_POP_BOND_BATCH;
     uint32_t et0[UB];
 #pragma unroll
-    for (int u = 0; u < UB; ++u) et0[u] = rebuilt ? 0u : g[(size_t)min(u, A.bdmax - 1) * 64];
+    for (int u = 0; u < UB; ++u) et0[u] = g[(size_t)min(u, A.bdmax - 1) * 64];
 #else
     constexpr int UB = IGM_POP_BOND_BATCH;
 #endif
@@ -2601,10 +2242,8 @@ __device__ __forceinline__ void pop_slot_force(const PopArgs& A, int s, int i, s
     };
     if (ri >= 0.0f) {
         if (nn == kNnbWalk) {
-            // the walk covers the cells around the position of the grid's build (with
-            // two-level lists the outer build: the cells hold the slots of that build)
-            const float4 b = A.two ? A.xo[base + i]
-                                   : make_float4(A.xb[base + i].x, A.xb[base + i].y, A.xb[base + i].z, 0.f);
+            // the walk covers the cells around the position of the grid's build
+            const pop_f3 b = A.xb[base + i];
             const float4 f = pop_walk_pairs(pos, A.cell + (size_t)s * kPopCells, A.gp + (size_t)s * 8,
                                             A.gn + (size_t)s * 8, b.x, b.y, b.z, i, p0, evfpi);
             fx = f.x;
@@ -2621,13 +2260,13 @@ __device__ __forceinline__ void pop_slot_force(const PopArgs& A, int s, int i, s
 #pragma unroll
                 for (int d = 1; d < QD; ++d) {
                     qb[d] = make_uint2(i * 0x10001u, i * 0x10001u);
-                    if (!rebuilt && nq > d) qb[d] = gl[(size_t)d * 64];
+                    if (nq > d) qb[d] = gl[(size_t)d * 64];
                 }
                 for (int q = 0; q < nq; ++q) {
-                    const uint2 e = rebuilt ? make_uint2(lrow[2 * q], lrow[2 * q + 1]) : qb[0];
+                    const uint2 e = qb[0];
 #pragma unroll
                     for (int d = 0; d + 1 < QD; ++d) qb[d] = qb[d + 1];
-                    if (!rebuilt && q + QD < nq) qb[QD - 1] = gl[(size_t)(q + QD) * 64];
+                    if (q + QD < nq) qb[QD - 1] = gl[(size_t)(q + QD) * 64];
                     const float4 a0 = fetch(e.x & 0xffffu), a1 = fetch(e.x >> 16), a2 = fetch(e.y & 0xffffu),
                                  a3 = fetch(e.y >> 16);
                     pair2(a0, a1);
@@ -2639,9 +2278,7 @@ __device__ __forceinline__ void pop_slot_force(const PopArgs& A, int s, int i, s
                     uint2 e[U];  // a quad past the list: the slot itself 4 times (no force)
 #pragma unroll
                     for (int u = 0; u < U; ++u)
-                        e[u] = q0 + u >= nq ? make_uint2(i * 0x10001u, i * 0x10001u)
-                               : rebuilt    ? make_uint2(lrow[2 * (q0 + u)], lrow[2 * (q0 + u) + 1])
-                                            : gl[(size_t)(q0 + u) * 64];
+                        e[u] = q0 + u >= nq ? make_uint2(i * 0x10001u, i * 0x10001u) : gl[(size_t)(q0 + u) * 64];
                     float4 pt[4 * U];
 #pragma unroll
                     for (int u = 0; u < U; ++u) {
@@ -2662,27 +2299,14 @@ __device__ __forceinline__ void pop_slot_force(const PopArgs& A, int s, int i, s
     }
     for (int k0 = 0; k0 < deg; k0 += UB) {
         uint32_t et[UB];
-        if (rebuilt) {  // atom-space entries -> slot-space (the permute of the unfused engine)
-#pragma unroll
-            for (int u = 0; u < UB; ++u) et[u] = ga[min(k0 + u, deg - 1)];
-            int sv[UB];
-#pragma unroll
-            for (int u = 0; u < UB; ++u) sv[u] = sl[et[u] & 0xffffu];
-#pragma unroll
-            for (int u = 0; u < UB; ++u) {
-                et[u] = (et[u] & 0xffff0000u) | (uint32_t)sv[u];
-                if (k0 + u < deg) g[(size_t)(k0 + u) * 64] = et[u];
-            }
-        } else {
 #if IGM_POP_PREFETCH
-            if (k0 == 0) {
+        if (k0 == 0) {
 #pragma unroll
-                for (int u = 0; u < UB; ++u) et[u] = u < deg ? et0[u] : et0[0];  // (past deg: a valid entry)
-            } else
+            for (int u = 0; u < UB; ++u) et[u] = u < deg ? et0[u] : et0[0];  // (past deg: a valid entry)
+        } else
 #endif
 #pragma unroll
-            for (int u = 0; u < UB; ++u) et[u] = g[(size_t)min(k0 + u, deg - 1) * 64];
-        }
+        for (int u = 0; u < UB; ++u) et[u] = g[(size_t)min(k0 + u, deg - 1) * 64];
         float4 pt[UB];
         float2 ct[UB];
 #pragma unroll
@@ -2732,12 +2356,6 @@ __device__ __forceinline__ void pop_slot_force(const PopArgs& A, int s, int i, s
 // when S.integrate; the run's setup evaluation otherwise).  (Measured on config C: a
 // block running the pairs and the bonds of its slots in separate waves at the same
 // time is 6 % slower than one thread per slot doing both.)
-//   FUSED: a structure whose list is rebuilt this step builds it here, a slot per
-// thread (pop_fill_slot into the thread's LDS row), and takes this step's pairs from
-// that row and its bonds from the atom-space adjacency (pop_slot_force's rebuilt
-// path): no fill launch, no list or bond re-read on rebuild steps.  Every cross-slot
-// input (the new slot order, cell offsets and positions) was written by the sort and
-// permute kernels before this launch.
 //   (Block windows staged in LDS, every neighbour inside them an LDS read instead of a
 // gather: round 5 with window-form lists, round 6 with the slot -> window mapping in this
 // kernel -- both slower on config C, profiles/r05_ab and profiles/r06_ab.)
@@ -2745,25 +2363,18 @@ struct PopArgsAn : PopArgs {
     AnchorsDev an;  // (aidx offset to the view's first structure, as the per-structure arrays)
 };
 
-template <bool FUSED, bool AN = false>
+template <bool AN = false>
 __global__ void __launch_bounds__(kPopBS, IGM_POP_FORCE_OCC) pop_force_kernel(std::conditional_t<AN, PopArgsAn, PopArgs> A,
                                                                               float evf, float envf, PopStep S) {
     __shared__ double red[kPopBS / 64];
-    __shared__ uint32_t lrow[FUSED ? kPopBS * kPopListRow / 2 : 1];
     const int lb = pop_block(), s = lb / A.nbs, blk = lb % A.nbs, i = blk * kPopBS + threadIdx.x;
     if (s >= A.cm.nstruct) return;
-    // the build kernels of this step are done (part 1 runs beside them: it leaves the counters)
-    if (S.part != 1 && blockIdx.x == 0 && threadIdx.x == 0) {
-        *A.nflag = 0;
-        if (A.two) *A.nflag2 = 0;
-    }
-    const int rebuilt = A.flag[S.fp][s];  // the structure's list is (was) rebuilt this step
-    if ((S.part == 1 && rebuilt) || (S.part == 2 && !rebuilt)) return;  // (block-uniform)
+    if (blockIdx.x == 0 && threadIdx.x == 0) *A.nflag = 0;  // the build kernels of this step are done
+    const int rebuilt = A.flag[S.fp][s];  // the structure's list was rebuilt this step
     if (i == 0) {
         A.nrebuild[s] += rebuilt ? 1 : 0;
         if (A.bc) A.bage[s] = rebuilt ? 0 : A.bage[s] + 1;
         A.flag[S.fp ^ 1][s] = 0;  // the next step's flags start clear
-        A.oflag[S.fp ^ 1][s] = 0;
     }
     const size_t base = (size_t)s * A.cm.ldn, k = base + i;
     const PopBuf& B = A.buf[A.par[s]];
@@ -2782,19 +2393,7 @@ __global__ void __launch_bounds__(kPopBS, IGM_POP_FORCE_OCC) pop_force_kernel(st
         pop_f3 v = B.vel[k];
         const uint32_t fl = B.flg[k];
         float fx, fy, fz;
-        if (FUSED && rebuilt) {
-            uint32_t* row = lrow + threadIdx.x * (kPopListRow / 2);
-            const float4 p0 = B.pos[k];
-            int nb = 0;
-            if (p0.w >= 0.0f)
-                nb = pop_fill_slot<false>(A, PopList{A.nl, A.nnb, A.kq}, s, i, base, B.pos + base, p0, row,
-                                          kPopListRow - 2);
-            else
-                A.nnb[k] = 0;
-            pop_slot_force<AN>(A, s, i, base, B.pos + base, fl, evf, envf, fx, fy, fz, (const IGM_LDS float2*)sbt, lds_types, anchors_of<AN>(A), row, nb);
-        } else {
-            pop_slot_force<AN>(A, s, i, base, B.pos + base, fl, evf, envf, fx, fy, fz, (const IGM_LDS float2*)sbt, lds_types, anchors_of<AN>(A));
-        }
+        pop_slot_force<AN>(A, s, i, base, B.pos + base, fl, evf, envf, fx, fy, fz, (const IGM_LDS float2*)sbt, lds_types, anchors_of<AN>(A));
         B.frc[k] = pop_f3{fx, fy, fz};
         if (S.integrate && !(fl & IGM_ATOM_FIXED)) {
             // final_integrate for the temperature only: the kicked velocity is not stored
@@ -2932,7 +2531,6 @@ __global__ void pop_flag_all_kernel(PopArgs A, int fp) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s < A.cm.nstruct) {
         A.flag[fp][s] = 1;
-        A.oflag[fp][s] = 1;
     }
 }
 
@@ -3953,37 +3551,21 @@ PopArgs pop_view(const PopArgs& Q, int s0, int ns, int g) {
     }
     V.inv = Q.inv + o;
     V.remap = Q.remap + o;
-    if (Q.ccnt) {
-        V.ccnt = Q.ccnt + (size_t)s0 * kPopCntStride;
-        V.tid = Q.tid + o;
-        V.ctot = Q.ctot + (size_t)s0 * 8;
-    }
     V.flag[0] = Q.flag[0] + s0;
     V.flag[1] = Q.flag[1] + s0;
-    V.oflag[0] = Q.oflag[0] + s0;
-    V.oflag[1] = Q.oflag[1] + s0;
     V.flist = Q.flist + s0;
-    V.flist2 = Q.flist2 + s0;
     V.nflag = Q.nflag + g;  // one build counter per group, each on its own stream
-    V.nflag2 = Q.nflag2 + g;
-    if (Q.two) {
-        V.xo = Q.xo + o;
-        V.nlo = Q.nlo + (size_t)s0 * nsl * Q.kqo * 64;
-        V.nnbo = Q.nnbo + o;
-    }
     V.nrebuild = Q.nrebuild + s0;
     V.kep = Q.kep + (size_t)s0 * Q.nbs;
     V.bbp = Q.bbp + (size_t)s0 * Q.nbs * 6;
     V.dofs = Q.dofs + s0;
-    V.coff = Q.coff + (size_t)s0 * (Q.cm.natom + 1);
-    V.cbase = Q.cbase + s0;
     return V;
 }
 
 // The population engine (HBM path): per step  integrate | [sort | permute | fill of the
 // flagged structures] | forces + final kick, over every slot of every structure.
 int run_anneal_pop(igm_ctx* c, const Prepared& pr, const AnnealArgs& A) {
-    const int S = pr.cm.nstruct, N = pr.cm.natom, ldn = pr.cm.ldn, nsl = pr.cm.nslice;
+    const int S = pr.cm.nstruct, N = pr.cm.natom, ldn = pr.cm.ldn;
     PopArgs Q;
     memset(&Q, 0, sizeof(Q));
     Q.cm = pr.cm;
@@ -4005,14 +3587,14 @@ int run_anneal_pop(igm_ctx* c, const Prepared& pr, const AnnealArgs& A) {
         // HBM of the engine's state, per slot: two parity buffers of (position 16, velocity
         // 12, force 12, atom id 4, slot 4, flags 1), build position 12, Verlet list 8 kq (512
         // B at the default 256 entries -- most of it), list length 2, bonds 2 x 4 bdmax, degree
-        // 2 x 2, slot remaps 8, pruned bonds 4 bdmax + 2; per structure the cell offsets.  At
+        // 2 x 2, pruned bonds 4 bdmax + 2, slot remaps 8; per structure the cell offsets.  At
         // config C (1000 x 29 839 slots) the lists alone are 15.3 GB.  Checked against the free
         // HBM (plus what this context's population workspace already holds) before anything
         // is allocated.  (Staged anchors -- 24 B each and 4 B per (structure, atom) -- were
         // allocated by prepare(): the free HBM read here already lacks them.)
         const size_t per_slot = 2 * (16 + 12 + 12 + 4 + 4 + 1) + 12 + 8 * (size_t)Q.kq + 2 + 12 * (size_t)Q.bdmax + 6 +
-                                8 + 4;
-        const size_t need = per_slot * SL + sizeof(int) * (size_t)S * (kPopCells + kPopCntStride);
+                                8;
+        const size_t need = per_slot * SL + sizeof(int) * (size_t)S * kPopCells;
         size_t held = 0;
         for (const auto& kv : c->ws)
             if (kv.first.compare(0, 4, "pop_") == 0) held += kv.second.second;
@@ -4057,36 +3639,11 @@ int run_anneal_pop(igm_ctx* c, const Prepared& pr, const AnnealArgs& A) {
     }
     IGM_TRY(workspace(c, "pop_flag", sizeof(int) * 2 * (size_t)S, &pfl));
     IGM_TRY(workspace(c, "pop_flist", sizeof(int) * (size_t)S, &pfli));
-    IGM_TRY(workspace(c, "pop_nflag", sizeof(int) * 2 * kPopMaxGroups, &pnf));
+    IGM_TRY(workspace(c, "pop_nflag", sizeof(int) * kPopMaxGroups, &pnf));
     IGM_TRY(workspace(c, "pop_ke", sizeof(double) * (size_t)S * Q.nbs, &pke));
     IGM_TRY(workspace(c, "pop_bb", sizeof(float) * 6 * (size_t)S * Q.nbs, &pbb));
     void* pnr = A.nrebuild;
     if (!pnr) IGM_TRY(workspace(c, "pop_nreb", sizeof(int) * (size_t)S, &pnr));
-    // two-level lists: the outer margin in units of the largest radius (0: one level)
-    const float rmax0 = 0.5f * (pr.P.cut_list - pr.P.skin);
-    float margin = 0.0f;
-    if (const char* e = getenv("IGM_POP_OUTER")) margin = (float)atof(e) * rmax0;
-    if (kPopFused) margin = 0.0f;
-    Q.two = margin > 0.0f ? 1 : 0;
-    constexpr int kOuterRow = kPopOuterCap + 2;
-    {
-        void *pfl2, *pfli2;
-        IGM_TRY(workspace(c, "pop_oflag", sizeof(int) * 2 * (size_t)S, &pfl2));
-        IGM_TRY(workspace(c, "pop_flist2", sizeof(int) * (size_t)S, &pfli2));
-        Q.oflag[0] = (int*)pfl2;
-        Q.oflag[1] = (int*)pfl2 + S;
-        Q.flist2 = (int*)pfli2;
-        if (Q.two) {
-            void *pxo, *pnlo, *pnnbo;
-            Q.kqo = kPopOuterCap / 4;
-            IGM_TRY(workspace(c, "pop_xo", sizeof(float4) * SL, &pxo));
-            IGM_TRY(workspace(c, "pop_nlo", sizeof(uint2) * SL * Q.kqo, &pnlo));
-            IGM_TRY(workspace(c, "pop_nnbo", sizeof(uint16_t) * SL, &pnnbo));
-            Q.xo = (float4*)pxo;
-            Q.nlo = (uint2*)pnlo;
-            Q.nnbo = (uint16_t*)pnnbo;
-        }
-    }
     Q.par = (int*)ppar;
     Q.xb = (pop_f3*)pxb;
     Q.nl = (uint2*)pnl;
@@ -4099,17 +3656,17 @@ int run_anneal_pop(igm_ctx* c, const Prepared& pr, const AnnealArgs& A) {
     Q.bdegb[0] = (uint16_t*)pbdeg;
     Q.bdegb[1] = (uint16_t*)pbdeg + SL;
     // bond pruning at list builds (the permute; IGM_POP_BOND_PRUNE=0 turns it off: a test
-    // switch -- the forces are bitwise the same either way).  Not with two-level lists (their
-    // inner builds move the build positions without a permute) nor the fused engine.
+    // switch -- the forces are bitwise the same either way).
     {
         const char* e = getenv("IGM_POP_BOND_PRUNE");
-        if ((e ? atoi(e) != 0 : true) && !Q.two && !kPopFused) {
+        if (e ? atoi(e) != 0 : true) {
             void *pbc, *pbcn, *pbpr;
             IGM_TRY(workspace(c, "pop_bc", sizeof(uint32_t) * SL * Q.bdmax, &pbc));
             IGM_TRY(workspace(c, "pop_bcn", sizeof(uint16_t) * SL, &pbcn));
             IGM_TRY(workspace(c, "pop_bpr", sizeof(int) * 2 * (size_t)S, &pbpr));
-            // ages start large: the first build prunes
-            IGM_HIP_CHECK(c, hipMemsetAsync(pbpr, 0x3f, sizeof(int) * 2 * (size_t)S, c->stream));
+            // every bond kept until a build says otherwise; ages start large: the first build prunes
+            IGM_HIP_CHECK(c, hipMemsetAsync(pbpr, 0, sizeof(int) * (size_t)S, c->stream));
+            IGM_HIP_CHECK(c, hipMemsetAsync((int*)pbpr + S, 0x3f, sizeof(int) * (size_t)S, c->stream));
             Q.bc = (uint32_t*)pbc;
             Q.bcn = (uint16_t*)pbcn;
             Q.bpr = (int*)pbpr;
@@ -4126,18 +3683,9 @@ int run_anneal_pop(igm_ctx* c, const Prepared& pr, const AnnealArgs& A) {
     Q.flag[1] = (int*)pfl + S;
     Q.flist = (int*)pfli;
     Q.nflag = (int*)pnf;
-    Q.nflag2 = (int*)pnf + kPopMaxGroups;
-    const bool sprof = IGM_POP_SORT_PROF && getenv("IGM_POP_SORT_PROF") != nullptr;  // profiling builds only
-    if (sprof) {
-        void* psp;
-        IGM_TRY(workspace(c, "pop_sprof", sizeof(unsigned long long) * 8, &psp));
-        IGM_HIP_CHECK(c, hipMemsetAsync(psp, 0, sizeof(unsigned long long) * 8, c->stream));
-        Q.sprof = (unsigned long long*)psp;
-    }
     Q.kep = (double*)pke;
     Q.bbp = (float*)pbb;
     Q.nrebuild = (int*)pnr;
-    (void)nsl;
     // dof of group nonfixed, per structure (atom flags may differ between structures)
     {
         const size_t nfl = pr.cm.afs ? (size_t)S * N : (size_t)N;
@@ -4158,50 +3706,12 @@ int run_anneal_pop(igm_ctx* c, const Prepared& pr, const AnnealArgs& A) {
         IGM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
         Q.dofs = (const double*)pdof;
     }
-    // bond rows as CSR (per-structure offsets by a block scan, structure bases on the host):
-    // the fused engine re-indexes bonds from atom space; the permute remaps slot space
-    if (kPopFused) {
-        void *pco, *pcb, *pcsr;
-        IGM_TRY(workspace(c, "pop_coff", sizeof(int) * (size_t)S * (N + 1), &pco));
-        hipLaunchKernelGGL(pop_csr_scan_kernel, dim3(S), dim3(1024), 0, c->stream, pr.cm.bonds.deg, N, (int*)pco);
-        std::vector<int> tot(S);
-        IGM_HIP_CHECK(c, hipMemcpy2DAsync(tot.data(), sizeof(int), (const int*)pco + N, sizeof(int) * (N + 1),
-                                          sizeof(int), S, hipMemcpyDeviceToHost, c->stream));
-        IGM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-        std::vector<int64_t> cb(S);
-        int64_t run = 0;
-        for (int st = 0; st < S; ++st) {
-            cb[st] = run;
-            run += tot[st];
-        }
-        IGM_TRY(workspace(c, "pop_cbase", sizeof(int64_t) * (size_t)S, &pcb));
-        IGM_TRY(workspace(c, "pop_csr", sizeof(uint32_t) * (size_t)(run > 0 ? run : 1), &pcsr));
-        IGM_HIP_CHECK(c, hipMemcpyAsync(pcb, cb.data(), sizeof(int64_t) * S, hipMemcpyHostToDevice, c->stream));
-        const int64_t nx = (int64_t)S * N;
-        hipLaunchKernelGGL(pop_csr_fill_kernel, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, c->stream,
-                           pr.cm.bonds, S, N, pr.cm.nslice, (const int*)pco, (const int64_t*)pcb, (uint32_t*)pcsr);
-        IGM_HIP_CHECK(c, hipGetLastError());
-        IGM_HIP_CHECK(c, hipStreamSynchronize(c->stream));  // cb (host) must outlive the copy
-        Q.coff = (const int*)pco;
-        Q.cbase = (const int64_t*)pcb;
-        Q.csr = (const uint32_t*)pcsr;
-    }
-    // the sort keeps its ids in LDS when they fit beside the cell counts (200 kb: 29 839 atoms)
     auto knob = [](const char* name, int dflt) {
         const char* e = getenv(name);
         return e ? atoi(e) : dflt;
     };
-    // The sort: the single-workgroup LDS sort (default) or the split sort (IGM_POP_SORT=1;
-    // both give the same slot order at the same cell cap, tests/test_mstep_paths_gpu.py).
-    // Measured on config C (profiles/r06_ab): the split sort is 6 % slower at 125 structures
-    // per GPU (full protocol: anneal 16.2 s against 15.3 s) and 16 % at pop = 1000 (protocol
-    // x0.05: 6.01 s against 5.18 s): it moves the counts, ids and cell offsets through HBM/L2
-    // in four launches where the LDS sort keeps them on one CU, and at these populations the
-    // other structure group hides the LDS sort's latency.  Two-level lists and the fused
-    // engine keep the LDS sort.  The split sort's counts live in HBM, so its grids take
-    // kPopCellCap cells whatever the structure's size; the LDS sort's cap is what its LDS holds.
-    const bool split = knob("IGM_POP_SORT", 0) != 0 && !Q.two && !kPopFused;
-    Q.ccap = split ? kPopCellCap : pop_sort_cells(N);
+    // the sort keeps its ids in LDS when they fit beside the cell counts (200 kb: 29 839 atoms)
+    Q.ccap = pop_sort_cells(N);
     {  // x cells per cell side (IGM_POP_QX: A/B only)
         const char* e = getenv("IGM_POP_QX");
         Q.qx = e ? std::max(1, std::min(4, atoi(e))) : kPopQx;
@@ -4213,21 +3723,6 @@ int run_anneal_pop(igm_ctx* c, const Prepared& pr, const AnnealArgs& A) {
                      : N <= 32 * kPopSortNT ? pop_sort_kernel<true, 32> : pop_sort_kernel<true, 0>;
     IGM_HIP_CHECK(c, hipFuncSetAttribute((const void*)sort_kern, hipFuncAttributeMaxDynamicSharedMemorySize,
                                          (int)sort_lds));
-    if (split) {
-        void *pcc, *ptd, *pct;
-        IGM_TRY(workspace(c, "pop_ccnt", sizeof(int) * (size_t)S * kPopCntStride, &pcc));
-        IGM_TRY(workspace(c, "pop_tid", sizeof(int) * SL, &ptd));
-        IGM_TRY(workspace(c, "pop_ctot", sizeof(int) * (size_t)S * 8, &pct));
-        IGM_HIP_CHECK(c, hipMemsetAsync(pcc, 0, sizeof(int) * (size_t)S * kPopCntStride, c->stream));
-        IGM_HIP_CHECK(c, hipMemsetAsync(pct, 0, sizeof(int) * (size_t)S * 8, c->stream));
-        Q.ccnt = (int*)pcc;
-        Q.tid = (int*)ptd;
-        Q.ctot = (int*)pct;
-    }
-    // structure slots of the build kernels' grids (IGM_POP_BUILD_SLOTS): a block loops over
-    // the flagged structures b / nbs, + slots, ..., so the grid need not cover every
-    // structure of the group (~1/6 of them rebuild at a step)
-    const int bslots = std::max(1, knob("IGM_POP_BUILD_SLOTS", 128));
     // Structure groups on auxiliary streams: while one group waits in its latency-bound
     // sort, the others' force and integrate launches fill the CUs (measured on config C:
     // 2 groups 11 % faster than 1, 4 and 8 slower).  Tuning knobs: IGM_POP_GROUPS groups,
@@ -4237,16 +3732,6 @@ int run_anneal_pop(igm_ctx* c, const Prepared& pr, const AnnealArgs& A) {
     ng = ng < 1 ? 1 : (ng > S ? S : (ng > kPopMaxGroups ? kPopMaxGroups : ng));
     nc = nc < 1 || nc > ng ? ng : nc;
     if (chunk <= 0) nc = ng;
-    // Forces ahead of the list builds (IGM_POP_EARLY=1, A/B only): the structures not rebuilt
-    // at a step need only the integrate before their force evaluation, so a second stream per
-    // group runs their forces (part 1) beside the flagged structures' sort, permute and fill,
-    // and the flagged ones' forces (part 2) follow the fill; the next integrate waits for both.
-    // Each structure is in exactly one part, so the results are bitwise those of one launch.
-    // Measured on config C (profiles/r06_ab): 125 structures 16.3-17.3 s anneal against 15.3 s,
-    // pop = 1000 (x0.05) 5.46 s against 5.17 s -- the steps are bound by the GPU's gather
-    // throughput, not by the groups' launch chains, so the shorter chain buys nothing and the
-    // second launch and cross-stream events cost.
-    const bool early = knob("IGM_POP_EARLY", 0) != 0 && !kPopFused;
     // the force launch of group g: with anchors staged the instantiation with the term, whose
     // arguments carry them (aidx offset to the group's first structure)
     const bool anchored = pr.an.aidx != nullptr;
@@ -4256,18 +3741,12 @@ int run_anneal_pop(igm_ctx* c, const Prepared& pr, const AnnealArgs& A) {
             PopArgsAn VA;
             static_cast<PopArgs&>(VA) = Vg;
             VA.an = AnchorsDev{pr.an.anch, pr.an.aidx + (size_t)s0 * N, pr.an.nanch + s0};
-            hipLaunchKernelGGL((pop_force_kernel<kPopFused, true>), grid, dim3(kPopBS), 0, sg, VA, evf, envf, ps);
+            hipLaunchKernelGGL((pop_force_kernel<true>), grid, dim3(kPopBS), 0, sg, VA, evf, envf, ps);
         } else {
-            hipLaunchKernelGGL((pop_force_kernel<kPopFused>), grid, dim3(kPopBS), 0, sg, Vg, evf, envf, ps);
+            hipLaunchKernelGGL((pop_force_kernel<>), grid, dim3(kPopBS), 0, sg, Vg, evf, envf, ps);
         }
     };
-    IGM_TRY(aux_streams(c, nc + (early ? ng : 0)));
-    std::vector<hipEvent_t> ev_int(early ? ng : 0), ev_frc(early ? ng : 0);
-    for (int g = 0; g < (early ? ng : 0); ++g) {
-        IGM_TRY(pop_event(c, 2 * g, &ev_int[g]));
-        IGM_TRY(pop_event(c, 2 * g + 1, &ev_frc[g]));
-    }
-    auto side = [&](int g) { return c->aux[nc + g]; };
+    IGM_TRY(aux_streams(c, nc));
     std::vector<PopArgs> V(ng);
     std::vector<int> g0(ng + 1);
     for (int g = 0; g <= ng; ++g) g0[g] = (int)((int64_t)S * g / ng);
@@ -4286,7 +3765,7 @@ int run_anneal_pop(igm_ctx* c, const Prepared& pr, const AnnealArgs& A) {
         pst = (unsigned long long*)p;
     }
     Timed tm(c, "anneal");
-    IGM_TRY(aux_fork(c, nc + (early ? ng : 0)));
+    IGM_TRY(aux_fork(c, nc));
     for (int g = 0; g < ng; ++g) {
         hipLaunchKernelGGL(pop_load_kernel, grid_of(g), blk, 0, strm(g), V[g], (const float*)A.xyz + g0[g] * n3);
         if (A.nseg == 0) {  // no runs (CG only): velocities 0, positions unchanged
@@ -4312,12 +3791,12 @@ int run_anneal_pop(igm_ctx* c, const Prepared& pr, const AnnealArgs& A) {
             if (*q == ',') ++q;
         }
     }
+    const float rmax0 = 0.5f * (pr.P.cut_list - pr.P.skin);
     float last_skin = pr.P.skin;
     for (int seg = 0; seg < A.nseg; ++seg) {
         if (seg_skin[seg] != last_skin || seg == 0) {  // a new cut: every list is rebuilt at the run's setup step
             for (int g = 0; g < ng; ++g) {
-                V[g].P.cut_list = 2.0f * rmax0 + seg_skin[seg] + margin;  // (two-level: the outer cut)
-                V[g].cut_in = 2.0f * rmax0 + seg_skin[seg];
+                V[g].P.cut_list = 2.0f * rmax0 + seg_skin[seg];
                 V[g].P.skin = seg_skin[seg];
                 hipLaunchKernelGGL(pop_flag_all_kernel, dim3((g0[g + 1] - g0[g] + 255) / 256), dim3(256), 0, strm(g),
                                    V[g], (int)(gbase & 1));
@@ -4336,7 +3815,6 @@ int run_anneal_pop(igm_ctx* c, const Prepared& pr, const AnnealArgs& A) {
         st.vlim = A.seg_xmax[seg] / A.dt;
         st.vlimsq = st.vlim * st.vlim;
         st.trig = 0.25f * seg_skin[seg] * seg_skin[seg];
-        st.trig_out = 0.25f * margin * margin;
         st.nsteps = A.seg_steps[seg];
         st.t0 = A.seg_t0[seg];
         st.t1 = A.seg_t1[seg];
@@ -4355,36 +3833,11 @@ int run_anneal_pop(igm_ctx* c, const Prepared& pr, const AnnealArgs& A) {
                     for (int g = w0; g < w0 + nc && g < ng; ++g) {
                         const int ns = g0[g + 1] - g0[g];
                         hipStream_t sg = strm(g);
-                        const dim3 bgrid(std::min(ns, bslots) * Q.nbs);  // the build kernels' grid
                         hipLaunchKernelGGL(pop_integrate_kernel, grid_of(g), blk, 0, sg, V[g], st);
-                        if (early) {  // the structures not rebuilt: forces beside the builds
-                            PopStep s1 = st;
-                            s1.part = 1;
-                            IGM_HIP_CHECK(c, hipEventRecord(ev_int[g], sg));
-                            IGM_HIP_CHECK(c, hipStreamWaitEvent(side(g), ev_int[g], 0));
-                            launch_force(V[g], g0[g], grid_of(g), side(g), evf, envf, s1);
-                            IGM_HIP_CHECK(c, hipEventRecord(ev_frc[g], side(g)));
-                        }
-                        if (split) {
-                            hipLaunchKernelGGL(pop_count_kernel, dim3(ns * Q.nbs), blk, 0, sg, V[g], st.fp);
-                            hipLaunchKernelGGL(pop_scan_kernel<kScanChunk / 8>, dim3(std::min(ns, bslots) * kScanChunks),
-                                               dim3(kScanChunk / 8), 0, sg, V[g]);
-                            hipLaunchKernelGGL(pop_scatter_kernel, bgrid, blk, 0, sg, V[g]);
-                            hipLaunchKernelGGL(pop_rank_kernel, bgrid, blk, 0, sg, V[g]);
-                        } else {
-                            hipLaunchKernelGGL(sort_kern, dim3(ns), dim3(kPopSortNT), sort_lds, sg, V[g], st.fp);
-                        }
-                        hipLaunchKernelGGL(pop_permute_kernel<!kPopFused>, dim3(ns * Q.nbs), blk, 0, sg, V[g]);
-                        if (Q.two) {
-                            hipLaunchKernelGGL(pop_fill_kernel<kOuterRow>, dim3(ns * Q.nbs), blk, 0, sg, V[g]);
-                            hipLaunchKernelGGL(pop_refilter_kernel, dim3(ns * Q.nbs), blk, 0, sg, V[g]);
-                        } else if (!kPopFused) {
-                            hipLaunchKernelGGL(pop_fill_kernel<kPopListRow>, dim3(ns * Q.nbs), blk, 0, sg, V[g]);
-                        }
-                        PopStep s2 = st;
-                        s2.part = early ? 2 : 0;
-                        launch_force(V[g], g0[g], grid_of(g), sg, evf, envf, s2);
-                        if (early) IGM_HIP_CHECK(c, hipStreamWaitEvent(sg, ev_frc[g], 0));  // (the next integrate)
+                        hipLaunchKernelGGL(sort_kern, dim3(ns), dim3(kPopSortNT), sort_lds, sg, V[g], st.fp);
+                        hipLaunchKernelGGL(pop_permute_kernel, dim3(ns * Q.nbs), blk, 0, sg, V[g]);
+                        hipLaunchKernelGGL(pop_fill_kernel, dim3(ns * Q.nbs), blk, 0, sg, V[g]);
+                        launch_force(V[g], g0[g], grid_of(g), sg, evf, envf, st);
                         if (pst && step % stats_every == 0)
                             hipLaunchKernelGGL(pop_stats_kernel, grid_of(g), blk, 0, sg, V[g], pst + 16 * seg);
                     }
@@ -4402,7 +3855,7 @@ int run_anneal_pop(igm_ctx* c, const Prepared& pr, const AnnealArgs& A) {
                                last && A.forces_out ? A.forces_out + g0[g] * n3 : nullptr);
     }
     IGM_HIP_CHECK(c, hipGetLastError());
-    IGM_TRY(aux_join(c, nc + (early ? ng : 0)));
+    IGM_TRY(aux_join(c, nc));
     if (pst) {
         std::vector<unsigned long long> v(16 * 2 * IGM_MAX_STAGES);
         IGM_HIP_CHECK(c, hipMemcpyAsync(v.data(), pst, sizeof(unsigned long long) * v.size(), hipMemcpyDeviceToHost,
@@ -4420,14 +3873,6 @@ int run_anneal_pop(igm_ctx* c, const Prepared& pr, const AnnealArgs& A) {
                     u[4] / n, u[6] / w, u[9] / nb, u[11], u[12] / nb, u[13] / nb, u[14] / nb,
                     u[15] / (double)(u[4] ? u[4] : 1));
         }
-    }
-    if (sprof) {
-        unsigned long long v[8];
-        IGM_HIP_CHECK(c, hipMemcpyAsync(v, Q.sprof, sizeof(v), hipMemcpyDeviceToHost, c->stream));
-        IGM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-        const double n = (double)(v[6] ? v[6] : 1);
-        fprintf(stderr, "[igm pop sort] %llu sorts; cycles per sort: grid %.0f count %.0f scan %.0f scatter %.0f rank %.0f "
-                        "offsets %.0f\n", v[6], v[0] / n, v[1] / n, v[2] / n, v[3] / n, v[4] / n, v[5] / n);
     }
     return IGM_OK;
 }

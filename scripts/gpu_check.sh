@@ -3,7 +3,7 @@
 # anneal A/B variants (VARIANTS, scripts/gpu_variants.sh with ARGS) and an optional kernel
 # trace (PROF=1: scripts/gpu_prof.sh with PARGS).  Every step under its own time limit;
 # the first failing step ends the call.
-#   TESTS="tests/test_mstep_paths_gpu.py" K="split_sort" VARIANTS=$'IGM_POP_SORT=1\nIGM_POP_SORT=0' \
+#   TESTS="tests/test_mstep_paths_gpu.py" K="build_variants" VARIANTS=$'IGM_POP_GROUPS=3\nIGM_POP_GROUPS=2' \
 #     ARGS="--config C --nstruct 125" bash scripts/gpu_check.sh
 cd "$GRAFT_REPO_ROOT" || exit 1
 OUT=gpurun_out/${TAG:-check}

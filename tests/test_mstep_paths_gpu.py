@@ -211,16 +211,12 @@ def _with_env(env, fn):
 
 def test_gpu_200kb_build_variants_bitwise_equal(ms, model200):
     """The population engine's list builds sort the slots by cell, ids ascending inside a
-    cell.  The single-workgroup LDS sort (the default) and the split sort (IGM_POP_SORT=1:
-    pop_count/scan/scatter/rank, several workgroups per flagged structure, counts in HBM)
-    give the same slot order, so a protocol run is bitwise the same on both; so is the
-    split sort with one structure slot in the build grids (IGM_POP_BUILD_SLOTS=1: every
-    block loops over the flagged structures), with 3 structure groups, and its rerun; and so
-    is the engine with the forces of the structures not rebuilt at a step running ahead of
-    the list builds on a second stream (IGM_POP_EARLY=1), and the engine without bond
-    pruning (IGM_POP_BOND_PRUNE=0: every bond visited at every step, the pruned ones adding
-    exactly 0) or pruning at every build (IGM_POP_PRUNE_AGE=0; default: builds whose lists
-    served >= 6 steps)."""
+    cell, and every per-structure sum is added in a fixed order, so a protocol run (with many
+    list builds) is bitwise the same on a rerun; so it is with the structures dealt over 3
+    groups (IGM_POP_GROUPS=3; default 2: other streams, other launch interleaving), and with
+    the engine without bond pruning (IGM_POP_BOND_PRUNE=0: every bond visited at every step,
+    the pruned ones adding exactly 0) or pruning at every build (IGM_POP_PRUNE_AGE=0;
+    default: builds whose lists served >= 6 steps)."""
     atoms, poly, prm, ptr, sb, x = model200
     n = 6
     x6 = np.concatenate([x] * 3)
@@ -236,17 +232,15 @@ def test_gpu_200kb_build_variants_bitwise_equal(ms, model200):
 
     def run():
         return ms.run(prm6, x6, atoms.radii, atoms.flags, poly, ptr6, sb6, seeds)
-    xs, is_ = _with_env({'IGM_POP_SORT': '1'}, run)
-    xl, il = run()
-    x1, i1 = _with_env({'IGM_POP_SORT': '1', 'IGM_POP_BUILD_SLOTS': '1', 'IGM_POP_GROUPS': '3'}, run)
-    xr, ir = _with_env({'IGM_POP_SORT': '1'}, run)
-    xe, ie = _with_env({'IGM_POP_EARLY': '1'}, run)
+    xd, id_ = run()
+    x3, i3 = _with_env({'IGM_POP_GROUPS': '3'}, run)
+    xr, ir = run()
     xp, ip = _with_env({'IGM_POP_BOND_PRUNE': '0'}, run)
     xa, ia = _with_env({'IGM_POP_PRUNE_AGE': '0'}, run)
-    assert np.all(is_['nrebuild'] > 10)  # many list builds
-    runs = {'lds sort': (xl, il), 'split sort, 1 build slot, 3 groups': (x1, i1), 'split sort rerun': (xr, ir),
-            'early forces': (xe, ie), 'no bond pruning': (xp, ip), 'pruning at every build': (xa, ia)}
-    bad = [k for k, (xo, io) in runs.items() if not (np.array_equal(xs, xo) and is_.tobytes() == io.tobytes())]
+    assert np.all(id_['nrebuild'] > 10)  # many list builds
+    runs = {'rerun': (xr, ir), '3 groups': (x3, i3), 'no bond pruning': (xp, ip),
+            'pruning at every build': (xa, ia)}
+    bad = [k for k, (xo, io) in runs.items() if not (np.array_equal(xd, xo) and id_.tobytes() == io.tobytes())]
     assert not bad, bad
 
 

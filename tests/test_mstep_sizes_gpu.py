@@ -236,8 +236,8 @@ def _short_protocol(steps=(60, 80, 80, 60), relax=20):
 @pytest.mark.parametrize('natom', DYN_SIZES)
 def test_gpu_protocol_short_every_engine(ms, natom):
     """The demo protocol at mdsteps (60, 80, 80, 60), relax 20: bitwise equal on a rerun,
-    finite, downhill.  At 65 and 1024 (population engine) also bitwise equal with the split
-    sort, 3 structure groups and without bond pruning, as the 200 kb model is held at 29 839."""
+    finite, downhill.  At 65 and 1024 (population engine) also bitwise equal with 3 structure
+    groups and without bond pruning, as the 200 kb model is held at 29 839."""
     atoms, poly, _, ptr, sb, x = _md_case(natom, 4)
     prm = M.params_from_cfg({'optimization': {'optimizer_options': _short_protocol()}}, sm.ENV_TWO)
     seeds = M.lammps_seeds(6535, list(range(4)), 3)
@@ -255,8 +255,7 @@ def test_gpu_protocol_short_every_engine(ms, natom):
     assert np.all((i0['final_energy'] < i0['einitial']) | (i0['einitial'] == 0.0))
     assert np.all(i0['final_energy'] <= i0['einitial']) and np.count_nonzero(i0['einitial'] > 0) >= 3
     if natom <= 1024:
-        variants = {'split sort': {'IGM_POP_SORT': '1'}, '3 groups': {'IGM_POP_GROUPS': '3'},
-                    'no bond pruning': {'IGM_POP_BOND_PRUNE': '0'}}
+        variants = {'3 groups': {'IGM_POP_GROUPS': '3'}, 'no bond pruning': {'IGM_POP_BOND_PRUNE': '0'}}
         bad = []
         for name, env in variants.items():
             xv, iv = _with_env(env, run)
