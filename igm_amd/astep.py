@@ -88,6 +88,18 @@ def _is_device(a):
     return hasattr(a, 'is_cuda') and a.is_cuda
 
 
+def row_capacity(pairs, copy_ptr, chrom):
+    """Rows the pairs can emit: min(|ii|, |jj|) for an intra pair, |ii|.|jj| for an inter pair
+    (ActivationDistanceStep.py:476-483).  A pair outside 0..nhap-1 or with i == j has no
+    combination: the library returns it with 0 rows."""
+    na = np.diff(np.asarray(copy_ptr, np.int64))
+    chrom = np.asarray(chrom)
+    pi, pj = np.asarray(pairs['i'], np.int64), np.asarray(pairs['j'], np.int64)
+    ok = (pi >= 0) & (pj >= 0) & (pi < len(na)) & (pj < len(na)) & (pi != pj)
+    pi, pj = pi[ok], pj[ok]
+    return int(np.where(chrom[pi] == chrom[pj], np.minimum(na[pi], na[pj]), na[pi] * na[pj]).sum())
+
+
 def compute_actdist(xyz, radii, copy_ptr, copy_idx, chrom, pairs, contact_range=2.0, it_corr=1,
                     device=0, return_per_pair=False, ctx=None):
     """Activation distances for every pair (one GPU call).
@@ -114,15 +126,7 @@ def compute_actdist(xyz, radii, copy_ptr, copy_idx, chrom, pairs, contact_range=
     assert radii.shape[0] == nbead and chrom.shape[0] >= nhap and copy_idx.shape[0] >= copy_ptr[-1]
     assert copy_idx.size == 0 or (copy_idx.min() >= 0 and copy_idx.max() < nbead)
     res = np.zeros(len(pairs), result_dtype)
-    # capacity: every pair's maximum row count
-    na = np.diff(copy_ptr)
-    if len(pairs):
-        ni = na[pairs['i']]
-        nj = na[pairs['j']]
-        same = chrom[pairs['i']] == chrom[pairs['j']]
-        cap = int(np.where(same, np.minimum(ni, nj), ni * nj).sum())
-    else:
-        cap = 0
+    cap = row_capacity(pairs, copy_ptr, chrom)
     rows = np.zeros(max(cap, 1), row_dtype)
     nout = ctypes.c_int64(0)
     rc = c.lib.igm_astep_actdist(c.h, 0, xyz.ctypes.data, nbead, S, radii.ctypes.data, copy_ptr.ctypes.data,
@@ -144,7 +148,14 @@ def _compute_actdist_device(c, xyz, radii, copy_ptr, copy_idx, chrom, pairs, con
     nhap = int(copy_ptr.shape[0]) - 1
     npairs = int(pairs.shape[0]) // pair_dtype.itemsize if pairs.dtype == torch.uint8 else int(pairs.shape[0])
     res = torch.empty(npairs * result_dtype.itemsize, dtype=torch.uint8, device=dev)
-    cap = int(npairs) * 4 if npairs else 1
+    # four rows a pair hold any genome with up to two copies per locus; with more copies the
+    # buffer is sized from the pair list (24 bytes a pair, read back once), like the host path
+    host_ptr = copy_ptr.cpu().numpy()
+    if npairs and np.diff(host_ptr).max(initial=0) > 2:
+        host_pairs = pairs.contiguous().view(torch.uint8).reshape(-1).cpu().numpy().view(pair_dtype)
+        cap = max(row_capacity(host_pairs, host_ptr, chrom.cpu().numpy()), 1)
+    else:
+        cap = int(npairs) * 4 if npairs else 1
     rows = torch.empty(cap * row_dtype.itemsize, dtype=torch.uint8, device=dev)
     nout = ctypes.c_int64(0)
     c.set_stream(torch.cuda.current_stream(dev).cuda_stream)

@@ -222,7 +222,8 @@ class AMIteration(object):
         # (S_total, natom, 3) -> (nbead, S_total, 3): the .hss / A-step layout
         self._call('igm_population_transpose', IGM_DEVICE_PTRS, self.nbead, self.S_total, self.natom, P(src),
                    P(self.pop_bm), 1)
-        cap = 4 * max(self.npairs, 1)
+        # every combination of a pair is a row: up to |ii|.|jj| of them, not four, past two copies
+        cap = max(int(self._combos[self.pair_lo:self.pair_hi].sum()), 1)
         rows = torch.empty(cap * row_dtype.itemsize, dtype=torch.uint8, device=self.dev)
         n = ctypes.c_int64(0)
         if self.npairs > 0:

@@ -77,7 +77,9 @@ typedef struct {
     double p;      /* corrected probability used (f64)                    */
     double pnow;   /* count(d^2 <= rcut^2) / (n*S)                        */
     int32_t o;     /* order statistic index, -1 if no rows                */
-    int32_t nrows; /* rows emitted for this pair (0, 1, 2 or 4 ...)       */
+    int32_t nrows; /* rows emitted: 0, or one per copy combination --     */
+                   /* min(|ii|,|jj|) intra, |ii|*|jj| inter (1..16 for    */
+                   /* up to four copies per locus)                        */
 } igm_pair_result;
 
 int igm_astep_actdist(igm_ctx* ctx, uint32_t flags,
