@@ -139,7 +139,21 @@ def rg2_f32(pts):
 def sprite_cluster_rg2(crd, hap_chrom, copy_ptr, copy_idx, cluster, reps, structs=None):
     """compute_gyration_radius (sprite.pyx:104-283) with the per-chromosome
     representatives given (they are np.random.choice draws in the reference, D9).
-    Returns rg2s (S,) f32 and selected beads (S, len(cluster))."""
+    Returns rg2s (S,) f32 and selected beads (S, len(cluster)).
+
+    Every Rg^2 the reference reports comes out of get_rg2s_cpp, whose running minimum
+    starts at INF = 1e8 with the copy selection at -1 and moves only on a strict <
+    (cpp_sprite_assignment.cpp:4,119-128): a value not below INF (NaN included) reads as
+    INF and selects nothing.
+      single chromosome: each copy group's Rg^2 is such a value (sprite.pyx:206-210) and
+        the first smallest group wins (np.argsort over <= 16 rows, :211-213), so groups
+        that are all at INF leave copy 0;
+      several chromosomes: with no combination of the representatives below INF the
+        selection stays -1 for every chromosome (cpp:120,133-136), and curr_beads[sel]
+        (sprite.pyx:272-274) indexes the LAST copy of every segment; the final Rg^2 of
+        the selected beads goes through get_rgs2 again (:282) and is capped the same way."""
+    inf = f32(1e8)
+    cap = lambda v: v if v < inf else inf
     cluster = np.sort(np.asarray(cluster))
     S = crd.shape[1]
     structs = range(S) if structs is None else structs
@@ -151,7 +165,7 @@ def sprite_cluster_rg2(crd, hap_chrom, copy_ptr, copy_idx, cluster, reps, struct
         nc = len(ci(cluster[0]))
         groups = [[ci(i)[k] for i in cluster] for k in range(nc)]
         for s in structs:
-            vals = [rg2_f32([crd[b, s] for b in g]) for g in groups]
+            vals = [cap(rg2_f32([crd[b, s] for b in g])) for g in groups]
             k = int(np.argmin(vals))  # first minimum
             rg[s], sel[s] = vals[k], groups[k]
         return rg, sel
@@ -162,7 +176,7 @@ def sprite_cluster_rg2(crd, hap_chrom, copy_ptr, copy_idx, cluster, reps, struct
         # get_rg2s_cpp on the representatives: mixed-radix combinations, strict <, first found
         alts = [[crd[b, s] for b in ci(r)] for r in reps]
         ncomb = int(np.prod([len(a) for a in alts]))
-        best, bestc = f32(1e8), None
+        best, bestc = inf, [-1] * len(alts)
         for k in range(ncomb):
             kk, comb = k, []
             for a in alts:
@@ -173,7 +187,7 @@ def sprite_cluster_rg2(crd, hap_chrom, copy_ptr, copy_idx, cluster, reps, struct
                 best, bestc = v, comb
         choice = {hap_chrom[r]: bestc[i] for i, r in enumerate(reps)}
         beads = [ci(seg)[choice[hap_chrom[seg]]] for seg in all_segments]
-        rg[s] = rg2_f32([crd[b, s] for b in beads])
+        rg[s] = cap(rg2_f32([crd[b, s] for b in beads]))
         sel[s] = beads
     return rg, sel
 

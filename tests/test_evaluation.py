@@ -112,11 +112,22 @@ def test_gpu_contact_counts_near_ties():
 
 @pytest.mark.gpu
 def test_gpu_haploid_counts_equal_summed_copies(pop):
-    """igm_contact_map_haploid (copies summed on the device) equals the diploid counts
-    summed over copy pairs on the host, exactly (integer sums), on the demo population;
-    reduce()'s matrix then follows by one division."""
+    """igm_contact_map_haploid (copies summed on the device) equals the oracle's counts
+    summed over copy pairs, exactly (integer sums), on the first 160 loci of the demo
+    population (both copies: 320 beads, five tiles); on the whole population it equals
+    the kernel's own diploid counts summed on the host; reduce()'s matrix then follows
+    by one division."""
     crd, r = pop['coordinates'], pop['radii']
     cp, ci = pop['copy_ptr'], pop['copy_idx']
+    nsub = 160
+    assert np.all(np.diff(cp[:nsub + 1]) == 2)
+    beads = np.concatenate([ci[cp[:nsub]], ci[cp[:nsub] + 1]])  # the copies 0, then the copies 1
+    sub, rsub = np.ascontiguousarray(crd[beads]), r[beads]
+    scp = np.arange(0, 2 * nsub + 1, 2, dtype=np.int32)
+    sci = np.column_stack([np.arange(nsub), np.arange(nsub) + nsub]).ravel().astype(np.int32)
+    want = EV.sum_copies(OA.contact_counts(sub, rsub, 2.0 * (1 + EV.EPS)).astype(np.float64), scp, sci)
+    got = EV.haploid_counts(sub, rsub, 2.0 * (1 + EV.EPS), scp, sci)
+    assert np.array_equal(got.astype(np.float64), want) and want.min() < want.max()
     full = EV.contact_counts(crd, r, 2.0 * (1 + EV.EPS))
     want = EV.sum_copies(full.astype(np.float64), cp, ci)
     got = EV.haploid_counts(crd, r, 2.0 * (1 + EV.EPS), cp, ci)
