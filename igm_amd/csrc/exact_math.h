@@ -32,8 +32,11 @@ __device__ __forceinline__ bool sqrt_le(float d2, float dist) {
 // float('%.Nf' % x) with scale = 10^N (N <= 15): CPython formats the exact binary
 // value rounded half-to-even to N decimals, and float() returns the double nearest
 // that decimal, i.e. RN(k / 10^N).  x*scale is split exactly into hi + lo.
+// A NaN prints as 'nan' whatever its sign and payload and reads back as the positive
+// quiet NaN; +-inf print and read back as themselves.
 __device__ __forceinline__ double round_dec(double x, double scale) {
-    if (!isfinite(x)) return x;
+    if (isnan(x)) return __longlong_as_double(0x7ff8000000000000LL);
+    if (isinf(x)) return x;
     const double hi = x * scale;
     const double lo = fma(x, scale, -hi);
     double r = rint(hi);

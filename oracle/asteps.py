@@ -45,13 +45,20 @@ def damid_d2(x, r, contact_range, shape, param):
     return (sq[:, 0] / f32(a * a) + sq[:, 1] / f32(b * b)) + sq[:, 2] / f32(c * c)
 
 
+result_dtype = np.dtype([('ad', '<f8'), ('p', '<f8'), ('pnow', '<f8'), ('o', '<i4'), ('nrows', '<i4')])
+
+
 def damid_actdist(crd, radii, copy_ptr, copy_idx, loci, profile, plast, it_corr, contact_range=0.05,
-                  shape='sphere', param=5000.0):
+                  shape='sphere', param=5000.0, return_per_locus=False):
     """Rows {loc, dist, prob} task() writes for the loci (in order), after the text
-    round trip.  crd: bead-major (N, S, 3) f32."""
+    round trip.  crd: bead-major (N, S, 3) f32.  profile / plast are indexed by the haploid
+    locus.  return_per_locus: also the record of every listed locus {ad, p, pnow, o, nrows} in
+    float64 before the text (ad NaN and o -1 where p <= 0; pnow is the contact fraction of the
+    population whatever it_corr is)."""
     rows = []
+    res = np.zeros(len(loci), result_dtype)
     S = crd.shape[1]
-    for I in loci:
+    for q, I in enumerate(loci):
         ii = [int(v) for v in copy_idx[copy_ptr[I]:copy_ptr[I + 1]]]
         nc = len(ii)
         p_exp, pl = f32(profile[I]), f32(plast[I])  # setup() stores (I, p_exp, plast) as float32 (:211-217)
@@ -60,15 +67,17 @@ def damid_actdist(crd, radii, copy_ptr, copy_idx, loci, profile, plast, it_corr,
         for i in range(nc):
             d_sq[i * S:(i + 1) * S] = damid_d2(crd[ii[i]], r, contact_range, shape, param)
         d_sq[::-1].sort()  # descending (:444)
+        pnow = float(np.count_nonzero(d_sq >= 1.0)) / (S * nc)
         if it_corr == 1:
-            pnow = float(np.count_nonzero(d_sq >= 1.0)) / (S * nc)
             p = _clean(p_exp, _clean(pnow, pl))
         else:
             p = float(p_exp)
         ad = 2
+        res[q] = (np.nan, p, pnow, -1, nc)
         if p > 0:
             o = min(nc * S - 1, int(np.round(np.float64(nc * S) * p)))  # round half to even
             ad = float(np.sqrt(d_sq[o]))
+            res[q]['ad'], res[q]['o'] = ad, o
         for i in ii:
             line = '%6d %.5f %.5f' % (i, ad, p)
             a, b, c = line.split()
@@ -76,7 +85,7 @@ def damid_actdist(crd, radii, copy_ptr, copy_idx, loci, profile, plast, it_corr,
     out = np.zeros(len(rows), [('loc', 'i4'), ('dist', 'f4'), ('prob', 'f4')])
     if rows:
         out['loc'], out['dist'], out['prob'] = zip(*rows)
-    return out
+    return (out, res) if return_per_locus else out
 
 
 def _rank(v):
