@@ -8,8 +8,8 @@
 //  * LDS path (natom <= 3072, the 2 Mb diploid model): float4 positions
 //    (x, y, z, radius) AND the Verlet list live in LDS; each thread owns BPT atoms
 //    (a = b*NT + t) and keeps their velocity, force and last-build position in
-//    VGPRs.  Per MD step: one barrier after the position update (fused with the
-//    neighbour-displacement vote, __syncthreads_or) and one for the temperature
+//    VGPRs.  Per MD step: one barrier after the position update (it carries the
+//    neighbour-displacement vote, block_vote) and one for the temperature
 //    sum of fix temp/rescale.  The only per-step HBM/L2 traffic left is the
 //    compact bond adjacency (4 B per bond end).
 //  * HBM path (larger structures, the 200 kb model with 29 838 beads): the same
@@ -1074,6 +1074,44 @@ __device__ __forceinline__ float temp_rescale_factor(double ke2, double dof, int
     return (float)sqrt(tt / tcur);
 }
 
+// The same factor in two parts, for a kernel whose whole block waits on it behind the
+// kinetic-energy barrier: temp_target is everything that does not need the sum (one of
+// the three divisions) and is computed ahead of the barrier; temp_rescale_from is what is
+// left behind it (two divisions and the root).  The expressions are those of
+// temp_rescale_factor, operation for operation, so the factor is bitwise the same.
+__device__ __forceinline__ double temp_target(int step, int nsteps, float t0, float t1) {
+    const double delta = (double)step / (double)nsteps;
+    return (double)t0 + delta * ((double)t1 - (double)t0);
+}
+__device__ __forceinline__ float temp_rescale_from(double ke2, double dof, double tt, double window, double fraction) {
+    const double tcur = dof > 0 ? ke2 / dof : 0.0;
+    if (!(tcur > 0.0)) return 1.0f;
+    if (!(fabs(tcur - tt) > window)) return 1.0f;
+    tt = tcur - fraction * (tcur - tt);
+    return (float)sqrt(tt / tcur);
+}
+
+// a block-uniform double held in scalar registers (also pins its computation where it
+// stands: a convergent operation is not sunk past a barrier towards its use)
+__device__ __forceinline__ double uniform_f64(double x) {
+    const unsigned long long u = __builtin_bit_cast(unsigned long long, x);
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ float uniform_f32(float x) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(uint32_t, x)));
+}
+// a uniform 32-bit value as the step loop sees it NOW: what is derived from it is computed
+// where it is written, not hoisted out of the loop into a register that lives (in the
+// anneal kernel: in scratch memory) across the force loop
+template <typename X>
+__device__ __forceinline__ X uniform_now(X x) {
+    uint32_t u = __builtin_amdgcn_readfirstlane(__builtin_bit_cast(uint32_t, x));
+    asm volatile("" : "+s"(u));
+    return __builtin_bit_cast(X, u);
+}
+
 // fix nve/limit half-kick with the velocity cap
 __device__ __forceinline__ void kick_limit(float& vx, float& vy, float& vz, float fx, float fy, float fz, float dtf,
                                            float vlim, float vlimsq) {
@@ -1115,6 +1153,53 @@ __device__ __forceinline__ float pick(const float (&arr)[BPT][3], int b, int d) 
     return r;
 }
 
+// ---- the two block-wide exchanges of an MD step of the LDS anneal kernel.  After
+// either barrier all waves of the block run the same dependent chain at the same time
+// (no other wave hides its latency), so both are written for the shortest chain: LDS
+// pointers typed as such (ds_* with immediate offsets, no generic-pointer checks) and
+// every load issued before the first one is waited on.
+typedef int igm_i4v __attribute__((ext_vector_type(4)));
+
+// Did any thread of the block move?  One barrier: a wave OR, one word per wave, the
+// barrier, then every thread ORs the NT/64 words.  `vote` (kMaxWaves ints, 16-byte
+// aligned) needs NO second barrier before it is written again, provided that between
+// two votes every wave passes another block barrier that follows its reads of the
+// first (the caller's argument is written at the call).
+template <int NT>
+__device__ __forceinline__ bool block_vote(int moved, IGM_LDS int* vote) {
+    static_assert(NT % 256 == 0 && NT / 64 <= kMaxWaves, "the words are read four at a time");
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;  // w: a scalar
+    const int wany = __builtin_amdgcn_ballot_w64(moved != 0) != 0ull ? 1 : 0;
+    if (lane == 0) vote[w] = wany;
+    __syncthreads();
+    const IGM_LDS igm_i4v* q = (const IGM_LDS igm_i4v*)vote;
+    igm_i4v x[NT / 256];
+#pragma unroll
+    for (int i = 0; i < NT / 256; ++i) x[i] = q[i];
+    igm_i4v o = x[0];
+#pragma unroll
+    for (int i = 1; i < NT / 256; ++i) o |= x[i];
+    return __builtin_amdgcn_readfirstlane((o.x | o.y) | (o.z | o.w)) != 0;
+}
+
+// block_sum<NT, 1> with the wave partials loaded together: the same partials added in the
+// same order (0.0 + red[0] + red[1] + ...), so the same bits
+template <int NT>
+__device__ __forceinline__ double block_sum_lds(double v, double* red_generic) {
+    IGM_LDS double* red = (IGM_LDS double*)red_generic;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;  // w: a scalar
+    v = wave_sum_f64(v);
+    if (lane == 0) red[w] = v;
+    __syncthreads();
+    double p[NT / 64];
+#pragma unroll
+    for (int i = 0; i < NT / 64; ++i) p[i] = red[i];
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < NT / 64; ++i) s += p[i];
+    return s;
+}
+
 // the arguments of the instantiations with the anchor term
 struct AnnealArgsAn : AnnealArgs {
     AnchorsDev an;
@@ -1125,6 +1210,10 @@ __global__ void __launch_bounds__(NT) anneal_kernel(std::conditional_t<AN, Annea
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int npad = NT * BPT;
     MdLds sm = carve_md_lds(smem, npad);
+    // the displacement vote's words: 64 B of the static reserve (kLdsBytes), not of the carve
+    __shared__ __attribute__((aligned(16))) int vote_words[kMaxWaves];
+    IGM_LDS int* vote = (IGM_LDS int*)vote_words;
+    IGM_LDS igm_f4v* posl = (IGM_LDS igm_f4v*)sm.pos;
     sm.L.gell = reinterpret_cast<uint16_t*>(A.ws + (size_t)blockIdx.x * A.ws_stride);  // list overflow (HBM)
     sm.L.kg = A.cm.kcap - kLdsListSlots;
     const int t = threadIdx.x, lane = t & 63;
@@ -1162,7 +1251,7 @@ __global__ void __launch_bounds__(NT) anneal_kernel(std::conditional_t<AN, Annea
         }
         double cnt[1] = {(double)nmob};
         block_sum<NT, 1>(cnt, sm.r.red0);
-        const double dof = 3.0 * cnt[0] - 3.0;  // compute temp of group nonfixed
+        const double dof = uniform_f64(3.0 * cnt[0] - 3.0);  // compute temp of group nonfixed
         __syncthreads();
         const uint32_t* adj = A.cm.bonds.ent + A.cm.bonds.base[s];
         const int* soff = A.cm.bonds.soff + (size_t)s * (A.cm.nslice + 1);
@@ -1205,35 +1294,65 @@ __global__ void __launch_bounds__(NT) anneal_kernel(std::conditional_t<AN, Annea
             const int nsteps = A.seg_steps[seg];
             const float evf = A.seg_evf[seg], envf = A.seg_envf[seg];
             const float t0 = A.seg_t0[seg], t1 = A.seg_t1[seg];
-            const float dtv = A.dt, dtf = 0.5f * A.dt;
-            const float vlim = A.seg_xmax[seg] / dtv;
-            const float vlimsq = vlim * vlim;
+            // the integrate loops' constants: uniform, but computed by the vector unit.  Left to the
+            // register allocator as vector registers they are candidates for scratch across the
+            // force loop (with the thermostat split they were spilled, and reloaded one wait at
+            // a time between the two barriers); as scalars they cost no memory access
+            const float dtv_s = A.dt, dtf_s = uniform_f32(0.5f * A.dt);
+            const float vlim_s = uniform_f32(A.seg_xmax[seg] / dtv_s);
+            const float vlimsq_s = uniform_f32(vlim_s * vlim_s);
             const float skin = A.seg_skin[seg];
-            const float trig = 0.25f * skin * skin;
+            const float trig_s = uniform_f32(0.25f * skin * skin);
             const float cut_list = A.P.cut_list - A.P.skin + skin;
             if (seg > 0 && skin != A.seg_skin[seg - 1])  // a new cut: rebuild at the run's setup step
 #pragma unroll
                 for (int b = 0; b < BPT; ++b) xb[b][0] = xb[b][1] = xb[b][2] = __int_as_float(0x7f800000);
             // ---- run nsteps: step 0 is Verlet::setup (forces only)
+            //
+            // Two block barriers per step, one per hazard on sm.pos: V (inside block_vote)
+            // between this step's position writes and the other threads' reads of them, and
+            // K (inside block_sum_lds; at step 0, which has no sum, the plain barrier in its
+            // place) between those reads and the next step's writes.  The same two barriers
+            // order the two small exchange buffers, neither of which has a barrier of its own
+            // after its reads:
+            //  * vote words: written before V, read right after V.  A wave writes them again
+            //    only in the next step, i.e. after it has passed this step's K (or step 0's
+            //    barrier), and a wave arrives at K only after its reads of the words (program
+            //    order: read, optional list build, forces, K).  The list build and the
+            //    profiling barrier lie between the reads and K and touch neither buffer's
+            //    hazard.  The last step of a segment ends with K and the next segment opens
+            //    with its step 0 vote; a segment of 0 steps ends with step 0's barrier; a
+            //    structure ends with the barriers around its output and next_structure().
+            //  * red0 (the 16 wave partials): written before K, read right after K, written
+            //    again in the next step after that step's V, which every wave reaches only
+            //    after its reads.  So one buffer serves every step (no red0/red1 alternation).
             for (int step = 0; step <= nsteps; ++step) {
                 int moved = 0;
+                // the thread's own atoms, which only it ever writes: loaded together (one wait, not
+                // one per atom).  (Loading the next step's ahead of the kinetic-energy barrier
+                // instead measured no faster: profiles/anneal_rest.)
+                float4 own[BPT];
+#pragma unroll
+                for (int b = 0; b < BPT; ++b) own[b] = lds_f4(posl, b * NT + t);
+                const float dtv = uniform_now(dtv_s), trig = uniform_now(trig_s);
+                float dtf = uniform_now(dtf_s), vlim = uniform_now(vlim_s), vlimsq = uniform_now(vlimsq_s);
 #pragma unroll
                 for (int b = 0; b < BPT; ++b) {
                     const int a = b * NT + t;
-                    float4 p = sm.pos[a];
+                    float4 p = own[b];
                     if (step > 0 && (mobile >> b & 1u)) {  // fix nve/limit: initial_integrate
                         kick_limit(v[b][0], v[b][1], v[b][2], f[b][0], f[b][1], f[b][2], dtf, vlim, vlimsq);
                         p.x += dtv * v[b][0];
                         p.y += dtv * v[b][1];
                         p.z += dtv * v[b][2];
-                        sm.pos[a] = p;
+                        posl[a] = igm_f4v{p.x, p.y, p.z, p.w};
                     }
                     if (p.w >= 0.0f) {
                         const float ddx = p.x - xb[b][0], ddy = p.y - xb[b][1], ddz = p.z - xb[b][2];
                         moved |= !(ddx * ddx + ddy * ddy + ddz * ddz <= trig);
                     }
                 }
-                if (__syncthreads_or(moved)) {  // neigh_modify every 1 check yes
+                if (block_vote<NT>(moved, vote)) {  // neigh_modify every 1 check yes
                     const unsigned long long c0 = A.prof ? clock64() : 0;
                     const unsigned long long cw = build_nlist_lds<NT>(natom, natom, sm.pos, sm.L, cut_list, sm.r);
                     if (A.prof) {
@@ -1288,16 +1407,22 @@ __global__ void __launch_bounds__(NT) anneal_kernel(std::conditional_t<AN, Annea
                     __syncthreads();  // setup forces read sm.pos: no update before every wave is done
                     continue;
                 }
-                double ts[1] = {0.0};
+                double ts = 0.0;
+                dtf = uniform_now(dtf_s), vlim = uniform_now(vlim_s), vlimsq = uniform_now(vlimsq_s);
 #pragma unroll
                 for (int b = 0; b < BPT; ++b) {  // final_integrate
                     if (!(mobile >> b & 1u)) continue;
                     kick_limit(v[b][0], v[b][1], v[b][2], f[b][0], f[b][1], f[b][2], dtf, vlim, vlimsq);
 #pragma unroll
-                    for (int d = 0; d < 3; ++d) ts[0] += (double)(v[b][d] * v[b][d]);
+                    for (int d = 0; d < 3; ++d) ts += (double)(v[b][d] * v[b][d]);
                 }
-                block_sum<NT, 1>(ts, (step & 1) ? sm.r.red1 : sm.r.red0);
-                const float factor = temp_rescale_factor(ts[0], dof, step, nsteps, t0, t1, A.t_window, A.t_fraction);
+                // fix temp/rescale: whatever does not need the sum goes ahead of its barrier, and
+                // what the chain behind the barrier reads is in scalar registers by then
+                const double tt = uniform_f64(temp_target(step, uniform_now(nsteps), uniform_now(t0), uniform_now(t1)));
+                const double twin = uniform_f64((double)uniform_now(A.t_window));
+                const double tfrac = uniform_f64((double)uniform_now(A.t_fraction));
+                const double ke2 = block_sum_lds<NT>(ts, sm.r.red0);
+                const float factor = temp_rescale_from(ke2, dof, tt, twin, tfrac);
                 if (factor != 1.0f)
 #pragma unroll
                     for (int b = 0; b < BPT; ++b)
