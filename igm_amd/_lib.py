@@ -127,6 +127,8 @@ SIGNATURES = {
                                  _vp, _vp, _vp, _vp]),
     'igm_tracing_assign': (_i32, [_vp, _u32, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32,
                                   _vp, _vp, _vp]),
+    'igm_tracing_assign_cells': (_i32, [_vp, _u32, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp,
+                                        _i32, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     'igm_mstep_run': (_i32, [_vp, _u32, ctypes.POINTER(MStepParams), _i32, _i32, _vp, _vp, _vp, _vp, _i64,
                              _vp, _vp, _vp, _vp]),
     'igm_mstep_forces': (_i32, [_vp, _u32, ctypes.POINTER(MStepParams), _i32, _i32, _vp, _vp, _vp, _vp, _i64,

@@ -432,7 +432,10 @@ class TracingAssignmentStep(Step):
     `ImagedLociAssignmentStep` commented out): every imaged trace of
     restraints/tracing/input_file is given the (structure, copy) of the current population it
     superposes best on -- the costs and the keep_best candidates on the GPU, the one-trace-per-
-    slot greedy assignment and the Kabsch targets on the host (igm_amd.tracing)."""
+    slot greedy assignment and the Kabsch targets on the host (igm_amd.tracing).  When the file
+    carries cell_ptr the traces of an imaged cell are placed jointly: one structure, one rigid
+    motion and one homologue labelling per cell (igm_tracing_assign_cells), one cell per
+    structure."""
 
     def __init__(self, cfg):
         rt = _runtime(cfg, 'tracing')
@@ -461,12 +464,20 @@ class TracingAssignmentStep(Step):
 
     def setup(self):
         store = PopulationStore(self.cfg['optimization']['structure_output'])
-        T = len(self._traces(store)['trace_ptr']) - 1
+        traces = self._traces(store)
+        self.tmp_extensions = ['.npz']
+        if traces['cell_ptr'] is not None:  # imaged cells: batches are ranges of cells
+            ncell = len(traces['cell_ptr']) - 1
+            bs = int(cget(self.cfg, 'optimization/kernel_opts/hip/tracing_cell_batch', 1 << 12))
+            self.argument_list = [{'batch': b, 'c0': c0, 'c1': min(c0 + bs, ncell),
+                                   'out': os.path.join(self.tmp_dir, '%s.%d.tracing.npz' % (self.uid, b))}
+                                  for b, c0 in enumerate(range(0, ncell, bs))]
+            return
+        T = len(traces['trace_ptr']) - 1
         bs = int(cget(self.cfg, 'optimization/kernel_opts/hip/tracing_batch', 1 << 14))
         self.argument_list = [{'batch': b, 't0': t0, 't1': min(t0 + bs, T),
                                'out': os.path.join(self.tmp_dir, '%s.%d.tracing.npz' % (self.uid, b))}
                               for b, t0 in enumerate(range(0, T, bs))]
-        self.tmp_extensions = ['.npz']
 
     def task(self, batch, device):
         """the batch's keep_best candidates as s * C + k with C the model's largest copy count
@@ -475,6 +486,15 @@ class TracingAssignmentStep(Step):
         store = PopulationStore(self.cfg['optimization']['structure_output'])
         traces = self._traces(store)
         S = store.nstruct
+        if 'c0' in batch:  # the batch's keep_best candidate structures per cell and the labels there
+            kb = min(int(rget(self.cfg, 'restraints/tracing/keep_best', 50)), S)
+            sub = tracing.slice_cells(traces, batch['c0'], batch['c1'])
+            cand, cost, label = _kernel(self.cfg, 'tracing_assign_cells')(store, sub, kb, device)
+            tmp = batch['out'] + '.part.npz'
+            np.savez(tmp, cand=np.asarray(cand, np.int64), cost=np.asarray(cost, np.float32),
+                     label=np.asarray(label, np.int64))
+            os.replace(tmp, batch['out'])
+            return
         kb = min(int(rget(self.cfg, 'restraints/tracing/keep_best', 50)), S * int(traces['ncopy'].min()))
         sub = tracing.slice_traces(traces, batch['t0'], batch['t1'])
         cand, rmsd = _kernel(self.cfg, 'tracing_assign')(store, sub, kb, device)
@@ -491,6 +511,8 @@ class TracingAssignmentStep(Step):
         from . import tracing
         store = PopulationStore(self.cfg['optimization']['structure_output'])
         traces = self._traces(store)
+        if traces['cell_ptr'] is not None:
+            return self._reduce_cells(store, traces)
         T = len(traces['trace_ptr']) - 1
         C = int(np.diff(store.copy_ptr).max())
         res = [np.load(b['out']) for b in self.argument_list]
@@ -511,6 +533,32 @@ class TracingAssignmentStep(Step):
         cset(self.cfg, 'runtime/tracing/n_unassigned', int(np.count_nonzero(pick < 0)))
         print('TracingAssignmentStep: %d of %d traces unassigned' % (int(np.count_nonzero(pick < 0)), T), flush=True)
 
+    def _reduce_cells(self, store, traces):
+        """imaged cells: a structure takes at most one cell (greedy over all batches), every
+        assigned cell is superposed as a whole; the same file, plus the per-cell datasets"""
+        from . import tracing
+        res = [np.load(b['out']) for b in self.argument_list]
+        cand, cost, label = (np.concatenate([r[k] for r in res]) for k in ('cand', 'cost', 'label'))
+        ncell = len(traces['cell_ptr']) - 1
+        pick = tracing.greedy_cell_assignment(cand, cost)
+        cell_structure = np.where(pick >= 0, cand[np.arange(ncell), np.maximum(pick, 0)], -1)
+        cell = np.repeat(np.arange(ncell), np.diff(traces['cell_ptr']))
+        structure = cell_structure[cell]
+        copy = np.where(structure >= 0, label[np.arange(len(cell)), np.maximum(pick, 0)[cell]], -1)
+        target, cell_fit, fit, _ = tracing.aligned_cell_targets(store.coordinates(), store.copy_ptr, store.copy_idx,
+                                                                traces, cell_structure, copy)
+        path = self._path()
+        suffix = ['tol_{:.4f}'.format(cget(self.cfg, 'runtime/tracing/tol'))]
+        if 'opt_iter' in self.cfg['runtime']:
+            suffix.append('iter_{}'.format(self.cfg['runtime']['opt_iter']))
+        _rotate(cget(self.cfg, 'runtime/tracing/assignment_file', None), path, suffix)
+        tracing.write_assignment(path, traces, store.copy_ptr, store.copy_idx, structure, copy, target, fit,
+                                 cell_structure=cell_structure, cell_rmsd=cell_fit)
+        cset(self.cfg, 'runtime/tracing/assignment_file', path)
+        cset(self.cfg, 'runtime/tracing/n_unassigned', int(np.count_nonzero(structure < 0)))
+        cset(self.cfg, 'runtime/tracing/n_cells_unassigned', int(np.count_nonzero(pick < 0)))
+        print('TracingAssignmentStep: %d of %d cells unassigned' % (int(np.count_nonzero(pick < 0)), ncell), flush=True)
+
     def skip(self):
         cset(self.cfg, 'runtime/tracing/assignment_file', self._path())
 
@@ -521,5 +569,11 @@ def _hip_tracing(store, traces, keep_best, device):
     return tracing.assign_costs(xyz, store.copy_ptr, store.copy_idx, traces, keep_best, ctx=_lib.context(device))
 
 
+def _hip_tracing_cells(store, traces, keep_best, device):
+    from . import _lib, tracing
+    xyz = np.ascontiguousarray(store.coordinates())
+    return tracing.assign_cell_costs(xyz, store.copy_ptr, store.copy_idx, traces, keep_best, ctx=_lib.context(device))
+
+
 KERNELS_HIP = {'damid': _hip_damid, 'nucldamid': _hip_nucldamid, 'fish': _hip_fish, 'sprite': _hip_sprite,
-               'polymer': _hip_polymer, 'tracing_assign': _hip_tracing}
+               'polymer': _hip_polymer, 'tracing_assign': _hip_tracing, 'tracing_assign_cells': _hip_tracing_cells}

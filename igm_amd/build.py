@@ -36,6 +36,7 @@ SOURCES = {
     'report_hic.hip': ['-ffp-contract=off'],
     # fp64 sums and a Jacobi eigenvalue: nothing is restated bit for bit, FMAs are welcome
     'tracing_assign.hip': [],
+    'tracing_cells.hip': [],
 }
 # host-only C++ (no device code): the .hss / actdist.hdf5 reader and writer
 HOST_SOURCES = {'h5io.cpp': []}

@@ -97,6 +97,8 @@ int igm_mstep_set_anchors(igm_ctx* c, int32_t nstruct, const int64_t* anchor_ptr
 
 double igm_last_kernel_ms(const igm_ctx* c, const char* name) {
     if (!c || !name) return -1.0;
+    auto sum = c->kms.find(name);
+    if (sum != c->kms.end()) return sum->second;
     auto it = c->kev.find(name);
     if (it == c->kev.end()) return -1.0;
     if (hipEventSynchronize(it->second.second) != hipSuccess) return -1.0;

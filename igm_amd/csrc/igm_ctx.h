@@ -20,6 +20,9 @@ struct igm_ctx {
     std::map<std::string, std::pair<void*, size_t>> ws;
     // per kernel family: (start, stop) events of its last launch on `stream`
     std::map<std::string, std::pair<hipEvent_t, hipEvent_t>> kev;
+    // per kernel family launched once per batch of one call: the event times of its launches
+    // summed by that call (igm_last_kernel_ms reads these before kev)
+    std::map<std::string, double> kms;
     // volumetric maps staged by igm_mstep_set_volumes (device copies live in ws slots
     // "vol_maps", "vol_vox", "vol_smap")
     int vol_nmap = 0, vol_nsmap = 0;

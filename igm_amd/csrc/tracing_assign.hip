@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "igm_ctx.h"
+#include "tracing_select.h"
 
 namespace {
 using namespace igm;
@@ -236,6 +237,19 @@ int pow2_at_least(int n) {
 
 }  // namespace
 
+int igm::tracing_select(igm_ctx* c, const float* cost, int rows, int N, int kb, int* best_cand, float* best_cost) {
+    if (N <= kSortMax) {
+        const int npad = pow2_at_least(N);
+        hipLaunchKernelGGL(tracing_select_sort_kernel, dim3((unsigned)rows), dim3(kBT),
+                           (size_t)npad * sizeof(unsigned long long), c->stream, cost, N, npad, kb, best_cand, best_cost);
+    } else {
+        hipLaunchKernelGGL(tracing_select_count_kernel, dim3((unsigned)rows), dim3(kBT), 0, c->stream, cost, N, kb,
+                           best_cand, best_cost);
+    }
+    IGM_HIP_CHECK(c, hipGetLastError());
+    return IGM_OK;
+}
+
 extern "C" int igm_tracing_assign(igm_ctx* c, uint32_t flags, const float* xyz, int32_t nbead, int32_t nstruct,
                                   const int32_t* copy_ptr, const int32_t* copy_idx, int32_t nhap, int32_t ntrace,
                                   const int64_t* trace_ptr, const int32_t* locus, const float* position,
@@ -363,16 +377,7 @@ extern "C" int igm_tracing_assign(igm_ctx* c, uint32_t flags, const float* xyz, 
         }
         {
             Timed tm(c, "tracing_select");
-            if (N <= kSortMax) {
-                const int npad = pow2_at_least(N);
-                hipLaunchKernelGGL(tracing_select_sort_kernel, dim3((unsigned)ntrace), dim3(kBT),
-                                   (size_t)npad * sizeof(unsigned long long), c->stream, (const float*)p_rmsd, N, npad,
-                                   (int)keep_best, d_bc, d_bv);
-            } else {
-                hipLaunchKernelGGL(tracing_select_count_kernel, dim3((unsigned)ntrace), dim3(kBT), 0, c->stream,
-                                   (const float*)p_rmsd, N, (int)keep_best, d_bc, d_bv);
-            }
-            IGM_HIP_CHECK(c, hipGetLastError());
+            IGM_TRY(tracing_select(c, (const float*)p_rmsd, ntrace, N, keep_best, d_bc, d_bv));
         }
     }
     IGM_TRY(to_host(c, flags, rmsd_out, (const float*)p_rmsd, (size_t)ntrace * N));

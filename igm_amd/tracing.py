@@ -32,6 +32,19 @@ and decides, from the current population, which (structure, copy) each trace is:
                      candidate (host, deterministic)
   aligned_targets    the assigned traces superposed on their beads (Kabsch, fp64, host)
   write_assignment   the assignment file the M-step reads
+
+Traces imaged in one cell share the cell's frame: with a fourth dataset
+
+    cell_ptr    (Ncell + 1,) the traces of cell c are cell_ptr[c] .. cell_ptr[c + 1]; at most C
+                             traces of a chromosome of C copies
+
+a cell is placed as a whole -- one structure, one rigid motion, one homologue labelling:
+
+  assign_cell_costs       per (cell, structure) the joint RMSD at the labelling an alternating
+                          search ends at, the keep_best cheapest structures per cell and the
+                          copy of every trace there, on the GPU (igm_tracing_assign_cells)
+  greedy_cell_assignment  a structure is one cell: it takes at most one
+  aligned_cell_targets    one Kabsch per assigned cell over all its spots
 """
 import numpy as np
 
@@ -110,10 +123,14 @@ def initial_coordinates(crd, data, sid, rng=None, init_noise=None):
 def check_traces(data, copy_ptr, hap_chrom):
     """The trace arrays validated against the model's index: {'trace_ptr' (T + 1,) int64,
     'locus' (n,) int32, 'position' (n, 3) float32 -- the precision the device reads --,
-    'chrom' (T,) the chromosome of every trace, 'ncopy' (T,) its number of copies}.
+    'chrom' (T,) the chromosome of every trace, 'ncopy' (T,) its number of copies, 'cell_ptr'
+    (Ncell + 1,) int64 or None: the traces cell_ptr[c] .. cell_ptr[c + 1] were imaged in cell c
+    and share its frame}.
     ValueError naming the first offending trace: a non-monotone trace_ptr, fewer than
     MIN_SPOTS spots, a locus outside [0, nhap), non-increasing loci, more than one chromosome,
-    a non-finite position."""
+    a non-finite position; naming the first offending cell: a cell_ptr that is not monotone,
+    does not span the traces or has an empty cell, more traces of a chromosome than it has
+    copies."""
     ptr = np.asarray(data['trace_ptr']).astype(np.int64).reshape(-1)
     locus = np.asarray(data['locus']).astype(np.int64).reshape(-1)
     position = np.asarray(data['position'], np.float64)
@@ -154,8 +171,34 @@ def check_traces(data, copy_ptr, hap_chrom):
     if not np.all(fin):
         raise ValueError('tracing input: trace %d has a non-finite position' % trace[np.where(~fin)[0][0]])
     first = locus[ptr[:-1]]
+    chrom, ncopy = np.asarray(ch[ptr[:-1]]), (copy_ptr[first + 1] - copy_ptr[first]).astype(np.int32)
+    cells = None if data.get('cell_ptr') is None else _check_cells(data['cell_ptr'], T, chrom, ncopy)
     return {'trace_ptr': ptr, 'locus': locus.astype(np.int32), 'position': position.astype(np.float32),
-            'chrom': np.asarray(ch[ptr[:-1]]), 'ncopy': (copy_ptr[first + 1] - copy_ptr[first]).astype(np.int32)}
+            'chrom': chrom, 'ncopy': ncopy, 'cell_ptr': cells}
+
+
+def _check_cells(cell_ptr, T, chrom, ncopy):
+    """cell_ptr (Ncell + 1,) int64 validated against the T traces: starts at 0, ends at T, every
+    cell with at least one trace and at most C traces of a chromosome of C copies"""
+    cp = np.asarray(cell_ptr).astype(np.int64).reshape(-1)
+    if len(cp) < 1 or cp[0] != 0:
+        raise ValueError('tracing input: cell_ptr must start at 0')
+    d = np.diff(cp)
+    if np.any(d < 0):
+        raise ValueError('tracing input: cell_ptr is not monotone at cell %d' % int(np.where(d < 0)[0][0]))
+    if np.any(d == 0):
+        raise ValueError('tracing input: cell %d has no trace' % int(np.where(d == 0)[0][0]))
+    if cp[-1] != T:
+        raise ValueError('tracing input: cell_ptr ends at %d, the file has %d traces' % (cp[-1], T))
+    names, cid = np.unique(chrom, return_inverse=True)
+    key = np.repeat(np.arange(len(d)), d) * max(len(names), 1) + cid  # (cell, chromosome), sorted by cell
+    uniq, first, count = np.unique(key, return_index=True, return_counts=True)
+    over = np.where(count > ncopy[first])[0]
+    if len(over):
+        t = int(first[over[0]])
+        raise ValueError('tracing input: cell %d has %d traces of chromosome %s, which has %d copies' % (
+            uniq[over[0]] // max(len(names), 1), count[over[0]], chrom[t], ncopy[t]))
+    return cp
 
 
 def read_traces(path, store):
@@ -164,6 +207,8 @@ def read_traces(path, store):
     from . import h5
     with h5.File(path) as f:
         data = {k: np.asarray(f.read(k)) for k in ('trace_ptr', 'locus', 'position')}
+        if 'cell_ptr' in f.keys():
+            data['cell_ptr'] = np.asarray(f.read('cell_ptr'))
     return check_traces(data, store.copy_ptr, store.hap_chrom)
 
 
@@ -263,11 +308,108 @@ def aligned_targets(xyz, copy_ptr, copy_idx, traces, structure, copy):
     return target, rmsd, rot
 
 
-def write_assignment(path, traces, copy_ptr, copy_idx, structure, copy, target, rmsd):
+# ---------------------------------------------------------------------------- imaged cells
+def slice_cells(traces, c0, c1):
+    """the cells c0 .. c1 as a trace set of their own"""
+    cp = traces['cell_ptr']
+    sub = slice_traces(traces, int(cp[c0]), int(cp[c1]))
+    sub['cell_ptr'] = cp[c0:c1 + 1] - cp[c0]
+    return sub
+
+
+def assign_cell_costs(xyz, copy_ptr, copy_idx, traces, keep_best, ctx=None, return_full=False, device=0,
+                      scratch_bytes=0):
+    """One igm_tracing_assign_cells call on the cells of `traces` (check_traces with cell_ptr):
+    best_struct (Ncell, keep_best) int32 and best_cost (Ncell, keep_best) float32 in increasing
+    order (ties to the lower structure), best_label (T, keep_best) uint8: the copy of every trace
+    at that candidate [, and the full cost (Ncell, S) float32, label (T, S) uint8 and rounds
+    (Ncell, S) uint8].  The cost of (cell, structure) is the RMSD of all the cell's spots under
+    ONE proper rigid motion and the homologue labelling the alternating search ends at
+    (include/igm_hip.h).  scratch_bytes: device scratch of the per-trace sums, 0 = 1 GiB."""
+    from . import _lib
+    c = ctx or _lib.context(device)
+    xyz = np.ascontiguousarray(xyz, np.float32)
+    assert xyz.ndim == 3 and xyz.shape[2] == 3, 'xyz must be (nbead, nstruct, 3)'
+    copy_ptr = np.ascontiguousarray(copy_ptr, np.int32)
+    copy_idx = np.ascontiguousarray(copy_idx, np.int32)
+    ptr = np.ascontiguousarray(traces['trace_ptr'], np.int64)
+    locus = np.ascontiguousarray(traces['locus'], np.int32)
+    pos = np.ascontiguousarray(traces['position'], np.float32)
+    cell_ptr = np.ascontiguousarray(traces['cell_ptr'], np.int64)
+    _, chrom = np.unique(np.asarray(traces['chrom']), return_inverse=True)
+    chrom = np.ascontiguousarray(chrom, np.int32)
+    T, nc, kb, S = len(ptr) - 1, len(cell_ptr) - 1, int(keep_best), xyz.shape[1]
+    bs = np.zeros((nc, max(kb, 0)), np.int32)
+    bv = np.zeros((nc, max(kb, 0)), np.float32)
+    bl = np.zeros((T, max(kb, 0)), np.uint8)
+    cost = np.zeros((nc, S), np.float32) if return_full else None
+    label = np.zeros((T, S), np.uint8) if return_full else None
+    rounds = np.zeros((nc, S), np.uint8) if return_full else None
+    rc = c.lib.igm_tracing_assign_cells(c.h, 0, xyz.ctypes.data, xyz.shape[0], S, copy_ptr.ctypes.data,
+                                        copy_idx.ctypes.data, len(copy_ptr) - 1, T, ptr.ctypes.data, _lib.ptr(locus),
+                                        _lib.ptr(pos), _lib.ptr(chrom), nc, cell_ptr.ctypes.data, kb,
+                                        int(scratch_bytes), _lib.ptr(cost), _lib.ptr(label), _lib.ptr(rounds),
+                                        bs.ctypes.data, bv.ctypes.data, bl.ctypes.data)
+    c.check(rc, 'igm_tracing_assign_cells')
+    return (bs, bv, bl, cost, label, rounds) if return_full else (bs, bv, bl)
+
+
+def greedy_cell_assignment(best_struct, best_cost):
+    """Which of its keep_best candidate structures every cell takes: pick (Ncell,) int64, the
+    column of best_struct, -1 for a cell left unassigned.  A structure is one cell, so it takes
+    at most one: the cells are visited in ascending (best_cost[c, 0], c) and each takes its first
+    free candidate."""
+    best_struct = np.asarray(best_struct)
+    best_cost = np.asarray(best_cost)
+    n = len(best_struct)
+    pick = np.full(n, -1, np.int64)
+    taken = set()
+    for c in np.lexsort((np.arange(n), best_cost[:, 0])) if n else []:
+        for j, s in enumerate(best_struct[c].tolist()):
+            if s not in taken:
+                taken.add(s)
+                pick[c] = j
+                break
+    return pick
+
+
+def aligned_cell_targets(xyz, copy_ptr, copy_idx, traces, cell_structure, copy):
+    """The assigned cells in the model's frame.  cell_structure (Ncell,): the structure of every
+    cell, -1 = unassigned; copy (T,): the homologue labelling of its traces.  One Kabsch (fp64,
+    determinant corrected) per cell over ALL its spots: target_i = R (p_i - mean p) + mean x.
+    Returns (target (n, 3) float64 with NaN rows for unassigned cells, cell_rmsd (Ncell,), the
+    RMSD of every trace on its own under the cell's motion (T,), rotation (Ncell, 3, 3))."""
+    ptr, cp = traces['trace_ptr'], traces['cell_ptr']
+    T, nc = len(ptr) - 1, len(cp) - 1
+    target = np.full((int(ptr[-1]), 3), np.nan)
+    cell_rmsd, trace_rmsd = np.full(nc, np.nan), np.full(T, np.nan)
+    rot = np.full((nc, 3, 3), np.nan)
+    copy_ptr = np.asarray(copy_ptr, np.int64)
+    locus = np.asarray(traces['locus'], np.int64)
+    for c in range(nc):
+        s = int(cell_structure[c])
+        if s < 0:
+            continue
+        t0, t1 = int(cp[c]), int(cp[c + 1])
+        a, b = int(ptr[t0]), int(ptr[t1])
+        k = np.repeat(np.asarray(copy[t0:t1], np.int64), np.diff(ptr[t0:t1 + 1]))
+        x = np.asarray(xyz[np.asarray(copy_idx)[copy_ptr[locus[a:b]] + k], s], np.float64)
+        p = np.asarray(traces['position'][a:b], np.float64)
+        rot[c], cell_rmsd[c] = kabsch(p, x)
+        target[a:b] = (p - p.mean(axis=0)) @ rot[c].T + x.mean(axis=0)
+        d2 = np.sum((target[a:b] - x) ** 2, axis=1)
+        trace_rmsd[t0:t1] = np.sqrt(np.add.reduceat(d2, ptr[t0:t1] - a) / np.diff(ptr[t0:t1 + 1]))
+    return target, cell_rmsd, trace_rmsd, rot
+
+
+def write_assignment(path, traces, copy_ptr, copy_idx, structure, copy, target, rmsd, cell_structure=None,
+                     cell_rmsd=None):
     """The assignment file of the M-step from an A-step result: the datasets read_assignment
     reads -- locus (the DIPLOID bead), target float64, assignment (the structure) -- over the
     spots of the assigned traces, by trace then by spot; 'trace' (per entry) and, per trace,
-    trace_structure, trace_copy (-1 = unassigned) and trace_rmsd (NaN)."""
+    trace_structure, trace_copy (-1 = unassigned) and trace_rmsd (NaN).  A run on imaged cells
+    (cell_structure given) adds trace_cell (T,), cell_structure and cell_rmsd (Ncell,), and its
+    trace_rmsd is every trace's own RMSD under its cell's motion."""
     from . import h5
     ptr = traces['trace_ptr']
     T = len(ptr) - 1
@@ -277,8 +419,13 @@ def write_assignment(path, traces, copy_ptr, copy_idx, structure, copy, target, 
     keep = structure[trace] >= 0
     copy_ptr = np.asarray(copy_ptr, np.int64)
     slot = copy_ptr[np.asarray(traces['locus'], np.int64)[keep]] + copy[trace[keep]]
-    h5.write(path, {'locus': np.asarray(copy_idx)[slot].astype(np.int64),
-                    'target': np.ascontiguousarray(np.asarray(target, np.float64)[keep]),
-                    'assignment': structure[trace[keep]], 'trace': trace[keep].astype(np.int64),
-                    'trace_structure': structure, 'trace_copy': np.where(structure >= 0, copy, -1),
-                    'trace_rmsd': np.asarray(rmsd, np.float64)})
+    out = {'locus': np.asarray(copy_idx)[slot].astype(np.int64),
+           'target': np.ascontiguousarray(np.asarray(target, np.float64)[keep]),
+           'assignment': structure[trace[keep]], 'trace': trace[keep].astype(np.int64),
+           'trace_structure': structure, 'trace_copy': np.where(structure >= 0, copy, -1),
+           'trace_rmsd': np.asarray(rmsd, np.float64)}
+    if cell_structure is not None:
+        out.update({'trace_cell': np.repeat(np.arange(len(traces['cell_ptr']) - 1), np.diff(traces['cell_ptr'])),
+                    'cell_structure': np.asarray(cell_structure, np.int64),
+                    'cell_rmsd': np.asarray(cell_rmsd, np.float64)})
+    h5.write(path, out)

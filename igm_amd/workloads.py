@@ -133,6 +133,53 @@ def synthetic_traces(store, xyz, ntrace, nspots, noise, seed):
     return {'trace_ptr': ptr, 'locus': locus, 'position': position}, structure, copy
 
 
+def synthetic_cells(store, xyz, ncell, nspots, noise, seed, missing=0.0):
+    """Imaged cells planted on the population xyz (nbead, S, 3) of `store`: cell c is one window
+    of nspots consecutive loci on every (chromosome, copy) of one structure -- the structures all
+    distinct -- under ONE random proper rotation, one translation of a few micrometres and
+    Gaussian noise (nm; a scalar or one value per cell).  The traces of a chromosome stand
+    together in shuffled order, and every homologue is dropped with probability `missing` (a
+    cell keeps at least one trace).  Returns ({'trace_ptr', 'locus', 'position' float32,
+    'cell_ptr'}, planted structure (ncell,), planted copy (T,))."""
+    get = (lambda k: store[k]) if isinstance(store, dict) else (lambda k: getattr(store, k))
+    copy_ptr, copy_idx, hap_chrom = (np.asarray(get(k)) for k in ('copy_ptr', 'copy_idx', 'hap_chrom'))
+    rng = np.random.default_rng(seed)
+    S = xyz.shape[1]
+    if ncell > S:
+        raise ValueError('%d cells do not fit %d structures' % (ncell, S))
+    ncopy = np.diff(copy_ptr)
+    noise = np.broadcast_to(np.asarray(noise, np.float64), (ncell,))
+    chroms = [c for c in np.unique(hap_chrom) if np.count_nonzero(hap_chrom == c) >= nspots]
+    structure = rng.choice(S, ncell, replace=False).astype(np.int64)
+    locus, position, copy, cell_ptr = [], [], [], [0]
+    for c in range(ncell):
+        s = int(structure[c])
+        rot, shift = random_rotation(rng), rng.normal(0.0, 3000.0, 3)
+        wins, x = [], []
+        for ch in chroms:
+            loci = np.where(hap_chrom == ch)[0]
+            for k in rng.permutation(int(ncopy[loci[0]])):
+                w0 = int(rng.integers(0, len(loci) - nspots + 1))
+                if rng.random() < missing:
+                    continue
+                wins.append((loci[w0:w0 + nspots], int(k)))
+                x.append(np.asarray(xyz[copy_idx[copy_ptr[wins[-1][0]] + k], s], np.float64))
+        if not wins:  # (every homologue dropped: the first chromosome's copy 0 stays)
+            loci = np.where(hap_chrom == chroms[0])[0][:nspots]
+            wins, x = [(loci, 0)], [np.asarray(xyz[copy_idx[copy_ptr[loci]], s], np.float64)]
+        centre = np.concatenate(x).mean(axis=0)
+        for (win, k), xt in zip(wins, x):
+            locus.append(win)
+            position.append((xt - centre) @ rot.T + shift + rng.normal(0.0, noise[c], xt.shape))
+            copy.append(k)
+        cell_ptr.append(len(copy))
+    traces = {'trace_ptr': np.arange(len(copy) + 1, dtype=np.int64) * nspots,
+              'locus': np.concatenate(locus).astype(np.int32),
+              'position': np.concatenate(position).astype(np.float32),
+              'cell_ptr': np.asarray(cell_ptr, np.int64)}
+    return traces, structure, np.asarray(copy, np.int64)
+
+
 def spec_D(pop, n, scale, ctx, nlocal=15000, nlong=1500, seed=41, hic=None):
     from . import assemble as A
     from . import damid

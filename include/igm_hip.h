@@ -240,6 +240,52 @@ int igm_tracing_assign(igm_ctx* ctx, uint32_t flags,
                        int32_t* best_cand,    /* (ntrace, keep_best): s * Cmax + k                        */
                        float* best_rmsd);     /* (ntrace, keep_best)                                      */
 
+/* Chromatin tracing on imaged cells: the traces cell_ptr[c]..cell_ptr[c+1] were imaged in one
+ * cell and share its frame (multiplexed FISH, seqFISH), so cell c is placed on structure s
+ * under ONE proper rigid motion and one homologue labelling L: every trace a copy of its
+ * chromosome, no copy of a chromosome twice.  trace_chrom[t] is the chromosome of trace t (any
+ * ids: the chromosome table is the caller's, as for igm_tracing_assign); a cell holds at most C
+ * traces of a chromosome of C copies.  With q_i the spots centred on the cell, x_i the beads
+ * minus the bead of the cell's first spot under copy 0, and per (trace, copy) the fp64 sums
+ * sx = sum x_i, sxx = sum |x_i|^2, m[a][b] = sum q_a x_b, the cost of L is
+ *   sqrt(max(0, (Ga + Gb - 2 lambda) / n)),  n = all spots, Ga = sum |q_i|^2, SX = sum sx(t, L_t),
+ *   Gb = max(0, sum sxx - |SX|^2 / n), lambda the largest eigenvalue of Horn's key matrix of
+ *   M = sum m(t, L_t); R the rotation of its unit eigenvector, tau = SX / n.
+ * L is found by a deterministic alternating search.  Start: per chromosome the injective
+ * labelling of least sum of e(t, k), the trace's own centred Kabsch residual.  Round: the joint
+ * (cost, R, tau) of L, then per chromosome the labelling of least sum of the residuals
+ *   r(t, k) = sqq_t + sxx + n_t |tau|^2 + 2 tau . (R sq_t) - 2 tau . sx - 2 sum_ab R_ba m_ab
+ * (sq_t, sqq_t: sum q_i, sum |q_i|^2 of the trace), taken only if strictly below the current
+ * labelling's.  Labellings go in lexicographic order of (copy of the chromosome's 1st trace,
+ * 2nd, ...), the first minimum wins.  The search stops when no chromosome moves or after 16
+ * rounds; the cost never increases, the end is a local optimum.
+ * Outputs: cost_out (ncell, nstruct) f32, label_out (ntrace, nstruct) the copy of every trace,
+ * rounds_out (ncell, nstruct) the re-labelling rounds made, the last of which moved nothing
+ * unless it was the 16th (all nullable); best_struct / best_cost (ncell, keep_best): the
+ * keep_best cheapest structures of every cell in increasing order, ties to the lower s;
+ * best_label (ntrace, keep_best): the copy of every trace at that candidate.
+ * The sums live in a device scratch of scratch_bytes (0: 1 GiB); the cells are processed in
+ * batches that fit it, and the outputs do not depend on the batching.
+ * IGM_E_INVALID: a malformed trace or cell_ptr, too many traces of a chromosome in a cell,
+ * keep_best < 1 or > nstruct.  IGM_E_UNSUPPORTED: a cell of more than 128 traces or a chromosome
+ * of more than 4 copies, a single cell whose sums do not fit scratch_bytes.  Host pointers only
+ * (validated on the host, before any launch).  Timings: igm_last_kernel_ms "tracing_cells"
+ * (= "tracing_cell_sums" + "tracing_cell_search" + "tracing_cell_select", each summed over the
+ * batches). */
+int igm_tracing_assign_cells(igm_ctx* ctx, uint32_t flags,
+                             const float* xyz, int32_t nbead, int32_t nstruct,
+                             const int32_t* copy_ptr, const int32_t* copy_idx, int32_t nhap,
+                             int32_t ntrace, const int64_t* trace_ptr, const int32_t* locus, const float* position,
+                             const int32_t* trace_chrom,
+                             int32_t ncell, const int64_t* cell_ptr,
+                             int32_t keep_best, int64_t scratch_bytes,
+                             float* cost_out,       /* (ncell, nstruct) f32 or NULL  */
+                             uint8_t* label_out,    /* (ntrace, nstruct) or NULL     */
+                             uint8_t* rounds_out,   /* (ncell, nstruct) or NULL      */
+                             int32_t* best_struct,  /* (ncell, keep_best)            */
+                             float* best_cost,      /* (ncell, keep_best) ascending, ties to the lower s */
+                             uint8_t* best_label);  /* (ntrace, keep_best)           */
+
 /* DamID lamina envelope membership (M-step restraint assembly, config D):
  * Damid._apply_envelope (igm/restraints/damid.py:112-143) for every structure at once.
  * out_flags[s, a] = base_flags[a] | (env_bit if some DamID row {loc = a, dist = d}
