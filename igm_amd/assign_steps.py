@@ -490,18 +490,17 @@ class TracingAssignmentStep(Step):
             kb = min(int(rget(self.cfg, 'restraints/tracing/keep_best', 50)), S)
             sub = tracing.slice_cells(traces, batch['c0'], batch['c1'])
             cand, cost, label = _kernel(self.cfg, 'tracing_assign_cells')(store, sub, kb, device)
-            tmp = batch['out'] + '.part.npz'
-            np.savez(tmp, cand=np.asarray(cand, np.int64), cost=np.asarray(cost, np.float32),
-                     label=np.asarray(label, np.int64))
-            os.replace(tmp, batch['out'])
-            return
-        kb = min(int(rget(self.cfg, 'restraints/tracing/keep_best', 50)), S * int(traces['ncopy'].min()))
-        sub = tracing.slice_traces(traces, batch['t0'], batch['t1'])
-        cand, rmsd = _kernel(self.cfg, 'tracing_assign')(store, sub, kb, device)
-        cb, C = int(sub['ncopy'].max()), int(np.diff(store.copy_ptr).max())
-        cand = np.asarray(cand, np.int64)
+            out = {'cand': np.asarray(cand, np.int64), 'cost': np.asarray(cost, np.float32),
+                   'label': np.asarray(label, np.int64)}
+        else:
+            kb = min(int(rget(self.cfg, 'restraints/tracing/keep_best', 50)), S * int(traces['ncopy'].min()))
+            sub = tracing.slice_traces(traces, batch['t0'], batch['t1'])
+            cand, rmsd = _kernel(self.cfg, 'tracing_assign')(store, sub, kb, device)
+            cb, C = int(sub['ncopy'].max()), int(np.diff(store.copy_ptr).max())
+            cand = np.asarray(cand, np.int64)
+            out = {'cand': (cand // cb) * C + cand % cb, 'rmsd': np.asarray(rmsd, np.float32)}
         tmp = batch['out'] + '.part.npz'
-        np.savez(tmp, cand=(cand // cb) * C + cand % cb, rmsd=np.asarray(rmsd, np.float32))
+        np.savez(tmp, **out)
         os.replace(tmp, batch['out'])
 
     def reduce(self):
@@ -523,15 +522,24 @@ class TracingAssignmentStep(Step):
         structure, copy = np.where(took >= 0, took // C, -1), np.where(took >= 0, took % C, -1)
         target, fit, _ = tracing.aligned_targets(store.coordinates(), store.copy_ptr, store.copy_idx, traces,
                                                  structure, copy)
+        self._write(store, traces, structure, copy, target, fit, pick, 'traces')
+
+    def _write(self, store, traces, structure, copy, target, fit, pick, unit, **cells):
+        """the end of both reduces: the previous file set aside, the new one written, the
+        runtime/tracing keys set; pick: per trace, or per cell with the per-cell datasets given"""
+        from . import tracing
         path = self._path()
         suffix = ['tol_{:.4f}'.format(cget(self.cfg, 'runtime/tracing/tol'))]
         if 'opt_iter' in self.cfg['runtime']:
             suffix.append('iter_{}'.format(self.cfg['runtime']['opt_iter']))
         _rotate(cget(self.cfg, 'runtime/tracing/assignment_file', None), path, suffix)
-        tracing.write_assignment(path, traces, store.copy_ptr, store.copy_idx, structure, copy, target, fit)
+        tracing.write_assignment(path, traces, store.copy_ptr, store.copy_idx, structure, copy, target, fit, **cells)
         cset(self.cfg, 'runtime/tracing/assignment_file', path)
-        cset(self.cfg, 'runtime/tracing/n_unassigned', int(np.count_nonzero(pick < 0)))
-        print('TracingAssignmentStep: %d of %d traces unassigned' % (int(np.count_nonzero(pick < 0)), T), flush=True)
+        cset(self.cfg, 'runtime/tracing/n_unassigned', int(np.count_nonzero(structure < 0)))
+        if cells:
+            cset(self.cfg, 'runtime/tracing/n_cells_unassigned', int(np.count_nonzero(pick < 0)))
+        print('TracingAssignmentStep: %d of %d %s unassigned' % (int(np.count_nonzero(pick < 0)), len(pick), unit),
+              flush=True)
 
     def _reduce_cells(self, store, traces):
         """imaged cells: a structure takes at most one cell (greedy over all batches), every
@@ -547,17 +555,8 @@ class TracingAssignmentStep(Step):
         copy = np.where(structure >= 0, label[np.arange(len(cell)), np.maximum(pick, 0)[cell]], -1)
         target, cell_fit, fit, _ = tracing.aligned_cell_targets(store.coordinates(), store.copy_ptr, store.copy_idx,
                                                                 traces, cell_structure, copy)
-        path = self._path()
-        suffix = ['tol_{:.4f}'.format(cget(self.cfg, 'runtime/tracing/tol'))]
-        if 'opt_iter' in self.cfg['runtime']:
-            suffix.append('iter_{}'.format(self.cfg['runtime']['opt_iter']))
-        _rotate(cget(self.cfg, 'runtime/tracing/assignment_file', None), path, suffix)
-        tracing.write_assignment(path, traces, store.copy_ptr, store.copy_idx, structure, copy, target, fit,
-                                 cell_structure=cell_structure, cell_rmsd=cell_fit)
-        cset(self.cfg, 'runtime/tracing/assignment_file', path)
-        cset(self.cfg, 'runtime/tracing/n_unassigned', int(np.count_nonzero(structure < 0)))
-        cset(self.cfg, 'runtime/tracing/n_cells_unassigned', int(np.count_nonzero(pick < 0)))
-        print('TracingAssignmentStep: %d of %d cells unassigned' % (int(np.count_nonzero(pick < 0)), ncell), flush=True)
+        self._write(store, traces, structure, copy, target, fit, pick, 'cells', cell_structure=cell_structure,
+                    cell_rmsd=cell_fit)
 
     def skip(self):
         cset(self.cfg, 'runtime/tracing/assignment_file', self._path())

@@ -7,8 +7,8 @@
 //            sums of squares, lambda the largest eigenvalue of Horn's 4x4 key matrix of the
 //            centred cross-covariance (Horn 1987, J. Opt. Soc. Am. A 4:629) -- a quaternion is
 //            always a proper rotation, so a mirrored trace does not score 0.  Everything is
-//            accumulated in fp64 from the f32 coordinates; lambda comes from cyclic Jacobi
-//            sweeps, which take any symmetric matrix (collinear and coincident spots included).
+//            accumulated in fp64 from the f32 coordinates; the sums and the eigen-solve are the
+//            ones igm_tracing_assign_cells uses too (tracing_common.h).
 //   select   per trace the keep_best smallest f32 costs over its S * Cmax candidates, ties to the
 //            lower candidate index s * Cmax + k: a bitonic sort of (cost bits, index) keys in LDS,
 //            and a counting pass once the keys no longer fit.
@@ -16,92 +16,27 @@
 // No atomics anywhere: the result is deterministic.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
-#include <cstdlib>
 #include <limits>
-#include <vector>
 
-#include "igm_ctx.h"
+#include "tracing_common.h"
 #include "tracing_select.h"
 
 namespace {
 using namespace igm;
 
-constexpr int kBT = 256;              // threads per workgroup (4 waves of 64)
-constexpr int kChunkDefault = 128;    // spots staged in LDS at a time
-constexpr int kChunkMax = 1024;
-constexpr int kMinSpots = 3;
 constexpr int kSortMax = 8192;        // candidates the LDS sort takes (64 KB of 8-byte keys)
 constexpr int kCountTile = 2048;      // costs the counting pass holds in LDS at a time
-constexpr int kSweeps = 10;           // Jacobi sweeps at most (a 4x4 converges in 4-6)
 
-struct CostArgs {
-    const float* xyz;        // (nbead, S, 3)
-    int S, Cmax, nsb;        // nsb: blocks of kBT structures
-    int chunk;
-    const long long* ptr;    // (T + 1) spots of trace t
-    const int* ncopy;        // (T) C_t
+struct CostArgs : SpotArgs {
     const double* ga;        // (T) centred sum of squares of the trace
-    const double* pos;       // (n, 3) centred positions
-    const int* bead;         // (n, Cmax) bead of spot i in copy k
     float* rmsd;             // (T, S, Cmax)
 };
 
-// one Jacobi rotation of the symmetric 4x4 a on the plane (P, Q)
-template <int P, int Q>
-__device__ __forceinline__ void jacobi_rotate(double (&a)[4][4]) {
-    const double apq = a[P][Q];
-    if (apq == 0.0) return;
-    const double theta = (a[Q][Q] - a[P][P]) / (2.0 * apq);
-    const double t = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));  // 0 for |theta| = inf
-    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-    a[P][P] -= t * apq;
-    a[Q][Q] += t * apq;
-    a[P][Q] = a[Q][P] = 0.0;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        if (r == P || r == Q) continue;
-        const double arp = a[r][P], arq = a[r][Q];
-        a[r][P] = a[P][r] = c * arp - s * arq;
-        a[r][Q] = a[Q][r] = s * arp + c * arq;
-    }
-}
-
-// largest eigenvalue of Horn's key matrix of the cross-covariance m[a][b] = sum p_a x_b
-__device__ double horn_lambda(const double (&m)[3][3]) {
-    double a[4][4];
-    a[0][0] = m[0][0] + m[1][1] + m[2][2];
-    a[1][1] = m[0][0] - m[1][1] - m[2][2];
-    a[2][2] = -m[0][0] + m[1][1] - m[2][2];
-    a[3][3] = -m[0][0] - m[1][1] + m[2][2];
-    a[0][1] = a[1][0] = m[1][2] - m[2][1];
-    a[0][2] = a[2][0] = m[2][0] - m[0][2];
-    a[0][3] = a[3][0] = m[0][1] - m[1][0];
-    a[1][2] = a[2][1] = m[0][1] + m[1][0];
-    a[1][3] = a[3][1] = m[2][0] + m[0][2];
-    a[2][3] = a[3][2] = m[1][2] + m[2][1];
-    for (int sweep = 0; sweep < kSweeps; ++sweep) {
-        const double off = a[0][1] * a[0][1] + a[0][2] * a[0][2] + a[0][3] * a[0][3] + a[1][2] * a[1][2] +
-                           a[1][3] * a[1][3] + a[2][3] * a[2][3];
-        const double dia = a[0][0] * a[0][0] + a[1][1] * a[1][1] + a[2][2] * a[2][2] + a[3][3] * a[3][3];
-        if (off <= 1e-30 * dia) break;  // |error of an eigenvalue| <= sqrt(2 off) (Weyl): 1.4e-15 relative
-        jacobi_rotate<0, 1>(a);
-        jacobi_rotate<0, 2>(a);
-        jacobi_rotate<0, 3>(a);
-        jacobi_rotate<1, 2>(a);
-        jacobi_rotate<1, 3>(a);
-        jacobi_rotate<2, 3>(a);
-    }
-    return fmax(fmax(a[0][0], a[1][1]), fmax(a[2][2], a[3][3]));
-}
-
-// One thread per (trace t, copy k, structure s), one block per (t, k, kBT structures): for one
-// bead the S structures are contiguous, so a wave reads 768 contiguous bytes per spot.  The
-// trace's centred positions and its beads go through LDS in chunks of A.chunk spots.
-__global__ void __launch_bounds__(kBT) tracing_cost_kernel(CostArgs A) {
-    extern __shared__ double tsm[];
-    double* sp = tsm;                                       // (chunk, 3)
-    int* sb = reinterpret_cast<int*>(tsm + 3 * A.chunk);    // (chunk)
+// One thread per (trace t, copy k, structure s), one block per (t, k, kBT structures): the sums of
+// spot_sums (tracing_common.h) on the positions centred on the trace, solved in place.  Held to 8
+// waves per SIMD (64 VGPRs): left to itself the scheduler clusters the four unrolled loads of the
+// sums, as it does in tracing_cell_sums_kernel, and the kernel drops to occupancy 5.
+__global__ void __launch_bounds__(kBT, 8) tracing_cost_kernel(CostArgs A) {
     const int sblk = blockIdx.x % A.nsb;
     const int tk = blockIdx.x / A.nsb;
     const int k = tk % A.Cmax, t = tk / A.Cmax;
@@ -114,51 +49,19 @@ __global__ void __launch_bounds__(kBT) tracing_cost_kernel(CostArgs A) {
     }
     const long long p0 = A.ptr[t];
     const int n = (int)(A.ptr[t + 1] - p0);
-    double x0[3] = {0.0, 0.0, 0.0};  // the structure's first bead: the sums run on x - x0
-    double sx[3] = {0.0, 0.0, 0.0}, sxx = 0.0;
-    double m[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
-    for (int c0 = 0; c0 < n; c0 += A.chunk) {
-        const int nc = min(A.chunk, n - c0);
-        __syncthreads();
-        for (int i = threadIdx.x; i < nc; i += kBT) {
-            const double* p = A.pos + (size_t)(p0 + c0 + i) * 3;
-            sp[3 * i] = p[0];
-            sp[3 * i + 1] = p[1];
-            sp[3 * i + 2] = p[2];
-            sb[i] = A.bead[(size_t)(p0 + c0 + i) * A.Cmax + k];
-        }
-        __syncthreads();
-        if (!live) continue;
-        if (c0 == 0) {
-            const float* q = A.xyz + ((size_t)sb[0] * A.S + s) * 3;
-            x0[0] = q[0];
-            x0[1] = q[1];
-            x0[2] = q[2];
-        }
-#pragma unroll 4
-        for (int i = 0; i < nc; ++i) {
-            const float* q = A.xyz + ((size_t)sb[i] * A.S + s) * 3;
-            const double x = (double)q[0] - x0[0], y = (double)q[1] - x0[1], z = (double)q[2] - x0[2];
-            const double px = sp[3 * i], py = sp[3 * i + 1], pz = sp[3 * i + 2];
-            sx[0] += x;
-            sx[1] += y;
-            sx[2] += z;
-            sxx += x * x + y * y + z * z;
-            m[0][0] += px * x;
-            m[0][1] += px * y;
-            m[0][2] += px * z;
-            m[1][0] += py * x;
-            m[1][1] += py * y;
-            m[1][2] += py * z;
-            m[2][0] += pz * x;
-            m[2][1] += pz * y;
-            m[2][2] += pz * z;
-        }
+    double x0[3] = {0.0, 0.0, 0.0};  // the bead of the trace's first spot: the sums run on x - x0
+    if (live) {
+        const float* q = A.xyz + ((size_t)A.bead[(size_t)p0 * A.Cmax + k] * A.S + s) * 3;
+        x0[0] = q[0];
+        x0[1] = q[1];
+        x0[2] = q[2];
     }
+    double sx[3], sxx, m[3][3], unused[4];
+    spot_sums(A, t, k, s, live, x0, sx, sxx, m);  // (block-collective: no thread has left)
     if (!live) return;
     // (the positions are centred, so sum p (x - xbar) = sum p x)
     const double gb = fmax(0.0, sxx - (sx[0] * sx[0] + sx[1] * sx[1] + sx[2] * sx[2]) / n);
-    const double lam = horn_lambda(m);
+    const double lam = horn<false>(m, unused);
     *out = (float)sqrt(fmax(0.0, (A.ga[t] + gb - 2.0 * lam) / n));
 }
 
@@ -263,53 +166,18 @@ extern "C" int igm_tracing_assign(igm_ctx* c, uint32_t flags, const float* xyz, 
         return fail(c, IGM_E_UNSUPPORTED, "igm_tracing_assign: host arrays expected (validated on the host)");
     IGM_HIP_CHECK(c, hipSetDevice(c->device));
     if (ntrace == 0) return IGM_OK;
-    // host validation: the kernels trust the tables built here
-    if (copy_ptr[0] != 0) return fail(c, IGM_E_INVALID, "igm_tracing_assign: copy_ptr[0] = %d, not 0", copy_ptr[0]);
-    for (int h = 0; h < nhap; ++h)
-        if (copy_ptr[h + 1] <= copy_ptr[h])
-            return fail(c, IGM_E_INVALID, "igm_tracing_assign: locus %d has no copies", h);
-    for (int q = 0; q < copy_ptr[nhap]; ++q)
-        if (copy_idx[q] < 0 || copy_idx[q] >= nbead)
-            return fail(c, IGM_E_INVALID, "igm_tracing_assign: bead %d outside [0, %d)", copy_idx[q], nbead);
-    if (trace_ptr[0] != 0)
-        return fail(c, IGM_E_INVALID, "igm_tracing_assign: trace_ptr[0] = %lld, not 0", (long long)trace_ptr[0]);
-    for (int t = 0; t < ntrace; ++t) {
-        if (trace_ptr[t + 1] < trace_ptr[t])
-            return fail(c, IGM_E_INVALID, "igm_tracing_assign: trace_ptr is not monotone at trace %d", t);
-        if (trace_ptr[t + 1] - trace_ptr[t] < kMinSpots)
-            return fail(c, IGM_E_INVALID, "igm_tracing_assign: trace %d has %lld spots, fewer than %d", t,
-                        (long long)(trace_ptr[t + 1] - trace_ptr[t]), kMinSpots);
-        if (trace_ptr[t + 1] - trace_ptr[t] > 0x7fffffff)
-            return fail(c, IGM_E_UNSUPPORTED, "igm_tracing_assign: trace %d has too many spots", t);
-    }
-    const int64_t nspot = trace_ptr[ntrace];
-    if (!locus || !position) return fail(c, IGM_E_INVALID, "igm_tracing_assign: locus or position is NULL");
-    std::vector<int> ncopy(ntrace);
-    std::vector<double> ga(ntrace), pos((size_t)nspot * 3);
+    std::vector<int> ncopy, bead;
+    IGM_TRY(check_traces(c, "igm_tracing_assign", nbead, copy_ptr, copy_idx, nhap, ntrace, trace_ptr, locus, position,
+                         locus && position ? nullptr : "locus or position", &ncopy));
+    // the positions centred on their trace
+    std::vector<double> ga(ntrace), pos((size_t)trace_ptr[ntrace] * 3);
     int Cmax = 1;
     int64_t cand_min = std::numeric_limits<int64_t>::max();
     for (int t = 0; t < ntrace; ++t) {
         const int64_t p0 = trace_ptr[t], p1 = trace_ptr[t + 1];
         double mean[3] = {0.0, 0.0, 0.0};
-        for (int64_t i = p0; i < p1; ++i) {
-            const int h = locus[i];
-            if (h < 0 || h >= nhap)
-                return fail(c, IGM_E_INVALID, "igm_tracing_assign: trace %d: locus %d outside [0, %d)", t, h, nhap);
-            if (i > p0 && h <= locus[i - 1])
-                return fail(c, IGM_E_INVALID, "igm_tracing_assign: trace %d: loci are not increasing", t);
-            const int nc = copy_ptr[h + 1] - copy_ptr[h];
-            // (the loci of one chromosome have one copy count; the chromosome table itself is the
-            // caller's, igm_amd.tracing.read_traces)
-            if (i > p0 && nc != ncopy[t])
-                return fail(c, IGM_E_INVALID, "igm_tracing_assign: trace %d: loci of more than one chromosome "
-                            "(copy counts %d and %d)", t, ncopy[t], nc);
-            ncopy[t] = nc;
-            for (int d = 0; d < 3; ++d) {
-                if (!std::isfinite(position[i * 3 + d]))
-                    return fail(c, IGM_E_INVALID, "igm_tracing_assign: trace %d: non-finite position", t);
-                mean[d] += (double)position[i * 3 + d];
-            }
-        }
+        for (int64_t i = p0; i < p1; ++i)
+            for (int d = 0; d < 3; ++d) mean[d] += (double)position[i * 3 + d];
         const double n = (double)(p1 - p0);
         double g = 0.0;
         for (int64_t i = p0; i < p1; ++i)
@@ -330,12 +198,7 @@ extern "C" int igm_tracing_assign(igm_ctx* c, uint32_t flags, const float* xyz, 
     if (N64 > 0x7fffffff || (int64_t)ntrace * Cmax * nsb > 0x7fffffff)
         return fail(c, IGM_E_UNSUPPORTED, "igm_tracing_assign: grid too large");
     const int N = (int)N64;
-    std::vector<int> bead((size_t)nspot * Cmax, 0);
-    for (int t = 0; t < ntrace; ++t)
-        for (int64_t i = trace_ptr[t]; i < trace_ptr[t + 1]; ++i)
-            for (int k = 0; k < ncopy[t]; ++k) bead[(size_t)i * Cmax + k] = copy_idx[copy_ptr[locus[i]] + k];
-    int chunk = kChunkDefault;
-    if (const char* e = getenv("IGM_TRACING_CHUNK")) chunk = std::min(kChunkMax, std::max(1, atoi(e)));  // (tests)
+    const int chunk = bead_table(copy_ptr, copy_idx, ntrace, trace_ptr, locus, ncopy, Cmax, &bead);
 
     const float* d_xyz;
     const int64_t* d_ptr;

@@ -21,56 +21,33 @@
 // (a thread only ever reads the records of its own cell and structure).
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cmath>
-#include <cstdlib>
-#include <vector>
-
-#include "igm_ctx.h"
+#include "tracing_common.h"
 #include "tracing_select.h"
 
 namespace {
 using namespace igm;
 
-constexpr int kBT = 256;              // threads per workgroup (4 waves of 64)
-constexpr int kChunkDefault = 128;    // spots staged in LDS at a time
-constexpr int kChunkMax = 1024;
-constexpr int kMinSpots = 3;
-constexpr int kSweeps = 10;           // Jacobi sweeps at most (a 4x4 converges in 4-6)
 constexpr int kRec = 13;              // doubles of a record: sx[3], sxx, m[3][3]
 constexpr int kCellRounds = 16;       // re-labelling rounds at most
 constexpr int kMaxCellTraces = 128;   // traces of a cell: 2 bits each in four 64-bit registers
 constexpr int kMaxCopies = 4;         // copies of a chromosome: up to 24 labellings
 constexpr int64_t kScratchDefault = 1ll << 30;
 
-struct SumsArgs {
-    const float* xyz;        // (nbead, S, 3)
-    int S, Cmax, nsb;        // nsb: blocks of kBT structures
-    int chunk;
+struct SumsArgs : SpotArgs {
     int t0;                  // first trace of the batch
-    const long long* ptr;    // (T + 1) spots of trace t
-    const int* ncopy;        // (T) C_t
     const int* ref;          // (T) the reference bead of the trace's cell
-    const double* pos;       // (n, 3) positions centred on their cell
-    const int* bead;         // (n, Cmax) bead of spot i in copy k
     double* rec;             // (traces of the batch, Cmax, kRec, S)
 };
 
-// One thread per (trace t, copy k, structure s), one block per (t, k, kBT structures): the access
-// pattern of tracing_cost_kernel (for one bead the S structures are contiguous, the trace's
-// positions and beads go through LDS in chunks), but the sums are stored, not solved.
+// One thread per (trace t, copy k, structure s), one block per (t, k, kBT structures): the sums of
+// spot_sums (tracing_common.h) on the positions centred on the cell, stored, not solved.
 __global__ void __launch_bounds__(kBT) tracing_cell_sums_kernel(SumsArgs A) {
-    extern __shared__ double tsm[];
-    double* sp = tsm;                                       // (chunk, 3)
-    int* sb = reinterpret_cast<int*>(tsm + 3 * A.chunk);    // (chunk)
     const int sblk = blockIdx.x % A.nsb;
     const int tk = blockIdx.x / A.nsb;
     const int k = tk % A.Cmax, tl = tk / A.Cmax, t = A.t0 + tl;
     const int s = sblk * kBT + threadIdx.x;
     const bool live = s < A.S;
     if (k >= A.ncopy[t]) return;  // (the whole block: the search never reads this record)
-    const long long p0 = A.ptr[t];
-    const int n = (int)(A.ptr[t + 1] - p0);
     double x0[3] = {0.0, 0.0, 0.0};
     if (live) {
         const float* q = A.xyz + ((size_t)A.ref[t] * A.S + s) * 3;
@@ -78,40 +55,8 @@ __global__ void __launch_bounds__(kBT) tracing_cell_sums_kernel(SumsArgs A) {
         x0[1] = q[1];
         x0[2] = q[2];
     }
-    double sx[3] = {0.0, 0.0, 0.0}, sxx = 0.0;
-    double m[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
-    for (int c0 = 0; c0 < n; c0 += A.chunk) {
-        const int nc = min(A.chunk, n - c0);
-        __syncthreads();
-        for (int i = threadIdx.x; i < nc; i += kBT) {
-            const double* p = A.pos + (size_t)(p0 + c0 + i) * 3;
-            sp[3 * i] = p[0];
-            sp[3 * i + 1] = p[1];
-            sp[3 * i + 2] = p[2];
-            sb[i] = A.bead[(size_t)(p0 + c0 + i) * A.Cmax + k];
-        }
-        __syncthreads();
-        if (!live) continue;
-#pragma unroll 4
-        for (int i = 0; i < nc; ++i) {
-            const float* q = A.xyz + ((size_t)sb[i] * A.S + s) * 3;
-            const double x = (double)q[0] - x0[0], y = (double)q[1] - x0[1], z = (double)q[2] - x0[2];
-            const double px = sp[3 * i], py = sp[3 * i + 1], pz = sp[3 * i + 2];
-            sx[0] += x;
-            sx[1] += y;
-            sx[2] += z;
-            sxx += x * x + y * y + z * z;
-            m[0][0] += px * x;
-            m[0][1] += px * y;
-            m[0][2] += px * z;
-            m[1][0] += py * x;
-            m[1][1] += py * y;
-            m[1][2] += py * z;
-            m[2][0] += pz * x;
-            m[2][1] += pz * y;
-            m[2][2] += pz * z;
-        }
-    }
+    double sx[3], sxx, m[3][3];
+    spot_sums(A, t, k, s, live, x0, sx, sxx, m);  // (block-collective: no thread has left)
     if (!live) return;
     const size_t S = (size_t)A.S;
     double* out = A.rec + ((size_t)tl * A.Cmax + k) * kRec * S + s;
@@ -123,83 +68,6 @@ __global__ void __launch_bounds__(kBT) tracing_cell_sums_kernel(SumsArgs A) {
     for (int a = 0; a < 3; ++a)
 #pragma unroll
         for (int b = 0; b < 3; ++b) out[(4 + 3 * a + b) * S] = m[a][b];
-}
-
-// one Jacobi rotation of the symmetric 4x4 a on the plane (P, Q); VEC: the rotations are
-// accumulated in v, whose column j is then the eigenvector of a[j][j]
-template <int P, int Q, bool VEC>
-__device__ __forceinline__ void jacobi_rotate(double (&a)[4][4], double (&v)[4][4]) {
-    const double apq = a[P][Q];
-    if (apq == 0.0) return;
-    const double theta = (a[Q][Q] - a[P][P]) / (2.0 * apq);
-    const double t = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));  // 0 for |theta| = inf
-    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-    a[P][P] -= t * apq;
-    a[Q][Q] += t * apq;
-    a[P][Q] = a[Q][P] = 0.0;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        if (VEC) {
-            const double vrp = v[r][P], vrq = v[r][Q];
-            v[r][P] = c * vrp - s * vrq;
-            v[r][Q] = s * vrp + c * vrq;
-        }
-        if (r == P || r == Q) continue;
-        const double arp = a[r][P], arq = a[r][Q];
-        a[r][P] = a[P][r] = c * arp - s * arq;
-        a[r][Q] = a[Q][r] = s * arp + c * arq;
-    }
-}
-
-// largest eigenvalue of Horn's key matrix of the cross-covariance m[a][b] = sum q_a x_b, and
-// (VEC) its unit eigenvector: the quaternion of the proper rotation R with x ~ R q
-template <bool VEC>
-__device__ double horn(const double (&m)[3][3], double (&quat)[4]) {
-    double a[4][4], v[4][4];
-    a[0][0] = m[0][0] + m[1][1] + m[2][2];
-    a[1][1] = m[0][0] - m[1][1] - m[2][2];
-    a[2][2] = -m[0][0] + m[1][1] - m[2][2];
-    a[3][3] = -m[0][0] - m[1][1] + m[2][2];
-    a[0][1] = a[1][0] = m[1][2] - m[2][1];
-    a[0][2] = a[2][0] = m[2][0] - m[0][2];
-    a[0][3] = a[3][0] = m[0][1] - m[1][0];
-    a[1][2] = a[2][1] = m[0][1] + m[1][0];
-    a[1][3] = a[3][1] = m[2][0] + m[0][2];
-    a[2][3] = a[3][2] = m[1][2] + m[2][1];
-    if (VEC) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) v[r][q] = r == q ? 1.0 : 0.0;
-    }
-    for (int sweep = 0; sweep < kSweeps; ++sweep) {
-        const double off = a[0][1] * a[0][1] + a[0][2] * a[0][2] + a[0][3] * a[0][3] + a[1][2] * a[1][2] +
-                           a[1][3] * a[1][3] + a[2][3] * a[2][3];
-        const double dia = a[0][0] * a[0][0] + a[1][1] * a[1][1] + a[2][2] * a[2][2] + a[3][3] * a[3][3];
-        if (off <= 1e-30 * dia) break;  // |error of an eigenvalue| <= sqrt(2 off) (Weyl): 1.4e-15 relative
-        jacobi_rotate<0, 1, VEC>(a, v);
-        jacobi_rotate<0, 2, VEC>(a, v);
-        jacobi_rotate<0, 3, VEC>(a, v);
-        jacobi_rotate<1, 2, VEC>(a, v);
-        jacobi_rotate<1, 3, VEC>(a, v);
-        jacobi_rotate<2, 3, VEC>(a, v);
-    }
-    double lam = a[0][0];
-    int j = 0;
-#pragma unroll
-    for (int q = 1; q < 4; ++q)
-        if (a[q][q] > lam) {
-            lam = a[q][q];
-            j = q;
-        }
-    if (VEC) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) quat[r] = j == 0 ? v[r][0] : j == 1 ? v[r][1] : j == 2 ? v[r][2] : v[r][3];
-        const double inv = 1.0 / sqrt(quat[0] * quat[0] + quat[1] * quat[1] + quat[2] * quat[2] + quat[3] * quat[3]);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) quat[r] *= inv;
-    }
-    return lam;
 }
 
 struct SearchArgs {
@@ -446,44 +314,12 @@ extern "C" int igm_tracing_assign_cells(igm_ctx* c, uint32_t flags, const float*
         return fail(c, IGM_E_INVALID, CELLS "cell_ptr ends at %lld, there are %d traces", (long long)cell_ptr[ncell],
                     ntrace);
     if (ntrace == 0) return IGM_OK;
-    if (copy_ptr[0] != 0) return fail(c, IGM_E_INVALID, CELLS "copy_ptr[0] = %d, not 0", copy_ptr[0]);
-    for (int h = 0; h < nhap; ++h)
-        if (copy_ptr[h + 1] <= copy_ptr[h]) return fail(c, IGM_E_INVALID, CELLS "locus %d has no copies", h);
-    for (int q = 0; q < copy_ptr[nhap]; ++q)
-        if (copy_idx[q] < 0 || copy_idx[q] >= nbead)
-            return fail(c, IGM_E_INVALID, CELLS "bead %d outside [0, %d)", copy_idx[q], nbead);
-    if (trace_ptr[0] != 0)
-        return fail(c, IGM_E_INVALID, CELLS "trace_ptr[0] = %lld, not 0", (long long)trace_ptr[0]);
-    for (int t = 0; t < ntrace; ++t) {
-        if (trace_ptr[t + 1] < trace_ptr[t])
-            return fail(c, IGM_E_INVALID, CELLS "trace_ptr is not monotone at trace %d", t);
-        if (trace_ptr[t + 1] - trace_ptr[t] < kMinSpots)
-            return fail(c, IGM_E_INVALID, CELLS "trace %d has %lld spots, fewer than %d", t,
-                        (long long)(trace_ptr[t + 1] - trace_ptr[t]), kMinSpots);
-        if (trace_ptr[t + 1] - trace_ptr[t] > 0x7fffffff)
-            return fail(c, IGM_E_UNSUPPORTED, CELLS "trace %d has too many spots", t);
-    }
+    std::vector<int> ncopy, bead;
+    IGM_TRY(check_traces(c, "igm_tracing_assign_cells", nbead, copy_ptr, copy_idx, nhap, ntrace, trace_ptr, locus,
+                         position, locus && position && trace_chrom ? nullptr : "locus, position or trace_chrom",
+                         &ncopy));
     const int64_t nspot = trace_ptr[ntrace];
-    if (!locus || !position || !trace_chrom)
-        return fail(c, IGM_E_INVALID, CELLS "locus, position or trace_chrom is NULL");
-    std::vector<int> ncopy(ntrace);
     int Cmax = 1;
-    for (int t = 0; t < ntrace; ++t)
-        for (int64_t i = trace_ptr[t]; i < trace_ptr[t + 1]; ++i) {
-            const int h = locus[i];
-            if (h < 0 || h >= nhap)
-                return fail(c, IGM_E_INVALID, CELLS "trace %d: locus %d outside [0, %d)", t, h, nhap);
-            if (i > trace_ptr[t] && h <= locus[i - 1])
-                return fail(c, IGM_E_INVALID, CELLS "trace %d: loci are not increasing", t);
-            const int nc = copy_ptr[h + 1] - copy_ptr[h];
-            if (i > trace_ptr[t] && nc != ncopy[t])
-                return fail(c, IGM_E_INVALID, CELLS "trace %d: loci of more than one chromosome (copy counts %d and %d)",
-                            t, ncopy[t], nc);
-            ncopy[t] = nc;
-            for (int d = 0; d < 3; ++d)
-                if (!std::isfinite(position[i * 3 + d]))
-                    return fail(c, IGM_E_INVALID, CELLS "trace %d: non-finite position", t);
-        }
     // the chromosomes of every cell, in order of first appearance, each with its traces in order
     std::vector<int> gptr(ncell + 1, 0), gchrom, gcopies, gtraces;
     std::vector<int2> grp;
@@ -544,7 +380,8 @@ extern "C" int igm_tracing_assign_cells(igm_ctx* c, uint32_t flags, const float*
         return fail(c, IGM_E_UNSUPPORTED, CELLS "grid too large");
     // the host tables: positions centred on their cell, the per-trace and per-cell sums, the beads
     std::vector<double> pos((size_t)nspot * 3), tstat((size_t)ntrace * 5), cstat((size_t)ncell * 2);
-    std::vector<int> ref(ntrace), tcell(ntrace), bead((size_t)nspot * Cmax, 0);
+    std::vector<int> ref(ntrace), tcell(ntrace);
+    const int chunk = bead_table(copy_ptr, copy_idx, ntrace, trace_ptr, locus, ncopy, Cmax, &bead);
     for (int q = 0; q < ncell; ++q) {
         const int64_t ta = cell_ptr[q], tb = cell_ptr[q + 1];
         const int64_t p0 = trace_ptr[ta], p1 = trace_ptr[tb];
@@ -555,15 +392,13 @@ extern "C" int igm_tracing_assign_cells(igm_ctx* c, uint32_t flags, const float*
         double Ga = 0.0;
         for (int64_t t = ta; t < tb; ++t) {
             double* ts = tstat.data() + (size_t)t * 5;
-            for (int64_t i = trace_ptr[t]; i < trace_ptr[t + 1]; ++i) {
+            for (int64_t i = trace_ptr[t]; i < trace_ptr[t + 1]; ++i)
                 for (int d = 0; d < 3; ++d) {
                     const double v = (double)position[i * 3 + d] - mean[d] / n;
                     pos[(size_t)i * 3 + d] = v;
                     ts[d] += v;
                     ts[3] += v * v;
                 }
-                for (int k = 0; k < ncopy[t]; ++k) bead[(size_t)i * Cmax + k] = copy_idx[copy_ptr[locus[i]] + k];
-            }
             ts[4] = (double)(trace_ptr[t + 1] - trace_ptr[t]);
             Ga += ts[3];
             ref[t] = copy_idx[copy_ptr[locus[p0]]];
@@ -572,8 +407,7 @@ extern "C" int igm_tracing_assign_cells(igm_ctx* c, uint32_t flags, const float*
         cstat[(size_t)q * 2] = Ga;
         cstat[(size_t)q * 2 + 1] = n;
     }
-    int chunk = kChunkDefault, max_rounds = kCellRounds;
-    if (const char* e = getenv("IGM_TRACING_CHUNK")) chunk = std::min(kChunkMax, std::max(1, atoi(e)));  // (tests)
+    int max_rounds = kCellRounds;
     // (scripts/tracing_cells_timing.py: the start alone, one round, two, ... to split the search's time)
     if (const char* e = getenv("IGM_TRACING_CELL_ROUNDS")) max_rounds = std::min(kCellRounds, std::max(0, atoi(e)));
 

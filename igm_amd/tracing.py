@@ -220,6 +220,16 @@ def slice_traces(traces, t0, t1):
             'ncopy': traces['ncopy'][t0:t1]}
 
 
+def _entry_arrays(xyz, copy_ptr, copy_idx, traces):
+    """(xyz, copy_ptr, copy_idx, trace_ptr, locus, position) contiguous and of the types both
+    library entries read"""
+    xyz = np.ascontiguousarray(xyz, np.float32)
+    assert xyz.ndim == 3 and xyz.shape[2] == 3, 'xyz must be (nbead, nstruct, 3)'
+    return (xyz, np.ascontiguousarray(copy_ptr, np.int32), np.ascontiguousarray(copy_idx, np.int32),
+            np.ascontiguousarray(traces['trace_ptr'], np.int64), np.ascontiguousarray(traces['locus'], np.int32),
+            np.ascontiguousarray(traces['position'], np.float32))
+
+
 def assign_costs(xyz, copy_ptr, copy_idx, traces, keep_best, ctx=None, return_full=False, device=0):
     """One igm_tracing_assign call: best_cand (T, keep_best) int32 = s * Cmax + k and best_rmsd
     (T, keep_best) float32 in increasing order (ties to the lower candidate), Cmax = the largest
@@ -227,13 +237,7 @@ def assign_costs(xyz, copy_ptr, copy_idx, traces, keep_best, ctx=None, return_fu
     xyz is the bead-major (nbead, S, 3) float32 population."""
     from . import _lib
     c = ctx or _lib.context(device)
-    xyz = np.ascontiguousarray(xyz, np.float32)
-    assert xyz.ndim == 3 and xyz.shape[2] == 3, 'xyz must be (nbead, nstruct, 3)'
-    copy_ptr = np.ascontiguousarray(copy_ptr, np.int32)
-    copy_idx = np.ascontiguousarray(copy_idx, np.int32)
-    ptr = np.ascontiguousarray(traces['trace_ptr'], np.int64)
-    locus = np.ascontiguousarray(traces['locus'], np.int32)
-    pos = np.ascontiguousarray(traces['position'], np.float32)
+    xyz, copy_ptr, copy_idx, ptr, locus, pos = _entry_arrays(xyz, copy_ptr, copy_idx, traces)
     T, kb, S = len(ptr) - 1, int(keep_best), xyz.shape[1]
     # (every locus of a trace has its trace's copy count; clipped: the library rejects a bad locus)
     cmax = int(np.diff(copy_ptr)[np.clip(locus, 0, len(copy_ptr) - 2)].max()) if len(locus) else 1
@@ -253,18 +257,24 @@ def greedy_assignment(best_cand, best_rmsd, trace_chain):
     candidate, trace_chain[t]: the chromosome of the trace) and takes at most one trace.  The
     traces are visited in ascending (best_rmsd[t, 0], t); each takes its first free candidate.
     best_cand of all traces must share one encoding (one Cmax)."""
-    best_cand = np.asarray(best_cand)
-    best_rmsd = np.asarray(best_rmsd)
     chain = np.asarray(trace_chain)
-    T = len(best_cand)
-    pick = np.full(T, -1, np.int64)
+    return _greedy(best_cand, best_rmsd, lambda t, cand: (cand, chain[t].item()))
+
+
+def _greedy(best, cost, slot):
+    """pick (n,) int64: the rows of best (n, keep_best) in ascending (cost[i, 0], i) each take the
+    first column j whose slot(i, best[i, j]) no earlier row has taken, -1 when none is free"""
+    best = np.asarray(best)
+    cost = np.asarray(cost)
+    n = len(best)
+    pick = np.full(n, -1, np.int64)
     taken = set()
-    for t in np.lexsort((np.arange(T), best_rmsd[:, 0])) if T else []:
-        for j, cand in enumerate(best_cand[t].tolist()):
-            slot = (cand, chain[t].item())
-            if slot not in taken:
-                taken.add(slot)
-                pick[t] = j
+    for i in np.lexsort((np.arange(n), cost[:, 0])) if n else []:
+        for j, cand in enumerate(best[i].tolist()):
+            key = slot(i, cand)
+            if key not in taken:
+                taken.add(key)
+                pick[i] = j
                 break
     return pick
 
@@ -280,6 +290,16 @@ def kabsch(p, x):
     R = U @ np.diag([1.0, 1.0, d]) @ Vt
     r = R @ pc.T - xc.T
     return R, float(np.sqrt(np.sum(r * r) / len(p)))
+
+
+def _superpose(xyz, copy_ptr, copy_idx, traces, a, b, k, s, target):
+    """The spots a .. b superposed on their beads in structure s, spot i on copy k (one copy, or
+    one per spot): writes target[a:b] = R (p - mean p) + mean x and returns (R, kabsch's rmsd, x)."""
+    x = np.asarray(xyz[np.asarray(copy_idx)[copy_ptr[traces['locus'][a:b]] + k], s], np.float64)
+    p = np.asarray(traces['position'][a:b], np.float64)
+    R, rmsd = kabsch(p, x)
+    target[a:b] = (p - p.mean(axis=0)) @ R.T + x.mean(axis=0)
+    return R, rmsd, x
 
 
 def aligned_targets(xyz, copy_ptr, copy_idx, traces, structure, copy):
@@ -298,13 +318,7 @@ def aligned_targets(xyz, copy_ptr, copy_idx, traces, structure, copy):
         s, k = int(structure[t]), int(copy[t])
         if s < 0:
             continue
-        a, b = int(ptr[t]), int(ptr[t + 1])
-        beads = np.asarray(copy_idx)[copy_ptr[traces['locus'][a:b]] + k]
-        x = np.asarray(xyz[beads, s], np.float64)
-        p = np.asarray(traces['position'][a:b], np.float64)
-        R, rmsd[t] = kabsch(p, x)
-        rot[t] = R
-        target[a:b] = (p - p.mean(axis=0)) @ R.T + x.mean(axis=0)
+        rot[t], rmsd[t], _ = _superpose(xyz, copy_ptr, copy_idx, traces, int(ptr[t]), int(ptr[t + 1]), k, s, target)
     return target, rmsd, rot
 
 
@@ -328,13 +342,7 @@ def assign_cell_costs(xyz, copy_ptr, copy_idx, traces, keep_best, ctx=None, retu
     (include/igm_hip.h).  scratch_bytes: device scratch of the per-trace sums, 0 = 1 GiB."""
     from . import _lib
     c = ctx or _lib.context(device)
-    xyz = np.ascontiguousarray(xyz, np.float32)
-    assert xyz.ndim == 3 and xyz.shape[2] == 3, 'xyz must be (nbead, nstruct, 3)'
-    copy_ptr = np.ascontiguousarray(copy_ptr, np.int32)
-    copy_idx = np.ascontiguousarray(copy_idx, np.int32)
-    ptr = np.ascontiguousarray(traces['trace_ptr'], np.int64)
-    locus = np.ascontiguousarray(traces['locus'], np.int32)
-    pos = np.ascontiguousarray(traces['position'], np.float32)
+    xyz, copy_ptr, copy_idx, ptr, locus, pos = _entry_arrays(xyz, copy_ptr, copy_idx, traces)
     cell_ptr = np.ascontiguousarray(traces['cell_ptr'], np.int64)
     _, chrom = np.unique(np.asarray(traces['chrom']), return_inverse=True)
     chrom = np.ascontiguousarray(chrom, np.int32)
@@ -359,18 +367,7 @@ def greedy_cell_assignment(best_struct, best_cost):
     column of best_struct, -1 for a cell left unassigned.  A structure is one cell, so it takes
     at most one: the cells are visited in ascending (best_cost[c, 0], c) and each takes its first
     free candidate."""
-    best_struct = np.asarray(best_struct)
-    best_cost = np.asarray(best_cost)
-    n = len(best_struct)
-    pick = np.full(n, -1, np.int64)
-    taken = set()
-    for c in np.lexsort((np.arange(n), best_cost[:, 0])) if n else []:
-        for j, s in enumerate(best_struct[c].tolist()):
-            if s not in taken:
-                taken.add(s)
-                pick[c] = j
-                break
-    return pick
+    return _greedy(best_struct, best_cost, lambda c, s: s)
 
 
 def aligned_cell_targets(xyz, copy_ptr, copy_idx, traces, cell_structure, copy):
@@ -385,7 +382,6 @@ def aligned_cell_targets(xyz, copy_ptr, copy_idx, traces, cell_structure, copy):
     cell_rmsd, trace_rmsd = np.full(nc, np.nan), np.full(T, np.nan)
     rot = np.full((nc, 3, 3), np.nan)
     copy_ptr = np.asarray(copy_ptr, np.int64)
-    locus = np.asarray(traces['locus'], np.int64)
     for c in range(nc):
         s = int(cell_structure[c])
         if s < 0:
@@ -393,10 +389,7 @@ def aligned_cell_targets(xyz, copy_ptr, copy_idx, traces, cell_structure, copy):
         t0, t1 = int(cp[c]), int(cp[c + 1])
         a, b = int(ptr[t0]), int(ptr[t1])
         k = np.repeat(np.asarray(copy[t0:t1], np.int64), np.diff(ptr[t0:t1 + 1]))
-        x = np.asarray(xyz[np.asarray(copy_idx)[copy_ptr[locus[a:b]] + k], s], np.float64)
-        p = np.asarray(traces['position'][a:b], np.float64)
-        rot[c], cell_rmsd[c] = kabsch(p, x)
-        target[a:b] = (p - p.mean(axis=0)) @ rot[c].T + x.mean(axis=0)
+        rot[c], cell_rmsd[c], x = _superpose(xyz, copy_ptr, copy_idx, traces, a, b, k, s, target)
         d2 = np.sum((target[a:b] - x) ** 2, axis=1)
         trace_rmsd[t0:t1] = np.sqrt(np.add.reduceat(d2, ptr[t0:t1] - a) / np.diff(ptr[t0:t1 + 1]))
     return target, cell_rmsd, trace_rmsd, rot
