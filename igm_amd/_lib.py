@@ -149,6 +149,9 @@ SIGNATURES = {
     'igm_report_levels': (_i32, [_vp, _u32, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp]),
     'igm_report_rg': (_i32, [_vp, _u32, _vp, _i32, _i32, _vp, _vp, _i32, _vp]),
     'igm_report_lamina': (_i32, [_vp, _u32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
+    'igm_report_map_levels': (_i32, [_vp, _u32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp,
+                                     _i32, _vp]),
+    'igm_report_map_lamina': (_i32, [_vp, _u32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp]),
     'igm_report_distance_map': (_i32, [_vp, _u32, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp]),
     'igm_report_hic': (_i32, [_vp, _u32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _f64, _f64,
                               _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),

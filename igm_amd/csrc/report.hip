@@ -4,6 +4,10 @@
 //   igm_report_rg            radius_of_gyration.py:9-41
 //   igm_report_lamina        damid.py:32-51
 //   igm_report_distance_map  distance_map.py:5-22
+// and, on an imaged nucleus (the maps of igm_mstep_set_volumes; this project's definitions,
+// the reference has no such report) --
+//   igm_report_map_levels    the level 1 - depth / depth scale, its means, density and shells
+//   igm_report_map_lamina    contacts with the lamina of a nucleus map or with a body
 // Compiled with -ffp-contract=off and the default correctly rounded f32 sqrt: every
 // per-element value is the reference's NumPy expression operation by operation, and
 // every floating-point sum has a fixed order (no floating-point atomics), so a rerun
@@ -12,6 +16,7 @@
 #include <cmath>
 
 #include "exact_math.h"
+#include "exp_map_depth.h"
 #include "igm_ctx.h"
 
 using namespace igm;
@@ -61,12 +66,62 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
     return s;
 }
 
+// The level source of pass 1 (compile time): what turns one (bead, structure) into its
+// level.  stage() runs once per structure tile on the whole workgroup, before a barrier.
+//   EllipsoidLevels  level_of on the semiaxes; no LDS, no depth
+//   MapLevels        1 - depth / depth scale, clamped at 0, on the structure's staged map:
+//                    the at most kLS map headers and scales of the tile sit in LDS, so a
+//                    (bead, structure) costs one 16-byte voxel load
+struct EllipsoidLevels {
+    static constexpr bool kMap = false;
+    double a, b, c;
+    __device__ __forceinline__ void stage(int, int, int) const {}
+    __device__ __forceinline__ double level(const float* p, int, double*) const {
+        return level_of(p[0], p[1], p[2], a, b, c);
+    }
+};
+
+struct MapLevels {
+    static constexpr bool kMap = true;
+    struct Lds {
+        ms::VolMapDev map[kLS];
+        double scale[kLS];
+        double depth[kLB][kLS + 1];
+    };
+    const ms::VolMapDev* maps;
+    const int4* vox;
+    const int* smap;      // (S) map of each structure, or NULL: map 0
+    const double* scale;  // (nmap) depth scale
+    __device__ static __forceinline__ Lds& lds() {
+        __shared__ Lds l;
+        return l;
+    }
+    __device__ __forceinline__ void stage(int s0, int ns, int t) const {
+        Lds& l = lds();
+        if (t < ns) {
+            const int m = smap ? smap[s0 + t] : 0;
+            l.map[t] = maps[m];
+            l.scale[t] = scale[m];
+        }
+    }
+    __device__ __forceinline__ double level(const float* p, int q, double* depth) const {
+        const Lds& l = lds();
+        const float x[3] = {p[0], p[1], p[2]};
+        const double d = exp_map_depth(x, l.map[q], vox);
+        *depth = d;
+        const double v = 1.0 - d / l.scale[q];
+        return v > 0.0 ? v : 0.0;  // off the centre of a deep voxel depth > scale: the sign bit stays clear
+    }
+};
+
 // Pass 1: a tile of kLB beads x kLS structures per step.  Levels go to lev (nstruct,
 // nbead) through an LDS transpose (both the reads and the writes are coalesced), the
 // per-bead sums run over the structures in order, the density counts collect in LDS.
-__global__ void __launch_bounds__(kRT) levels_kernel(const float* __restrict__ xyz, int n, int S, double a, double b,
-                                                     double c, double* __restrict__ lev,
-                                                     double* __restrict__ level_mean,
+// The map source also sums the signed depths per bead, in the same order.
+template <class Src>
+__global__ void __launch_bounds__(kRT) levels_kernel(const float* __restrict__ xyz, int n, int S, Src src,
+                                                     double* __restrict__ lev, double* __restrict__ level_mean,
+                                                     double* __restrict__ depth_mean,
                                                      const double* __restrict__ edges, int nbins,
                                                      u64* __restrict__ density) {
     __shared__ double tile[kLB][kLS + 1];
@@ -75,16 +130,20 @@ __global__ void __launch_bounds__(kRT) levels_kernel(const float* __restrict__ x
     const bool lds_hist = density && nbins <= kMaxLdsBins;
     if (lds_hist)
         for (int k = t; k < nbins; k += kRT) hist[k] = 0;
-    double sum = 0.0;
+    double sum = 0.0, dsum = 0.0;
     for (int s0 = 0; s0 < S; s0 += kLS) {
         const int ns = min(kLS, S - s0);
         __syncthreads();
+        if constexpr (Src::kMap) {
+            src.stage(s0, ns, t);
+            __syncthreads();
+        }
         for (int e = t; e < kLB * kLS; e += kRT) {
             const int r = e / kLS, q = e - r * kLS;
-            double v = 0.0;
+            double v = 0.0, dep = 0.0;
             if (b0 + r < n && q < ns) {
                 const float* p = xyz + ((size_t)(b0 + r) * S + s0 + q) * 3;
-                v = level_of(p[0], p[1], p[2], a, b, c);
+                v = src.level(p, q, &dep);
                 if (density) {
                     const int k = bin_of(edges, nbins, v);
                     if (k >= 0) {
@@ -94,6 +153,7 @@ __global__ void __launch_bounds__(kRT) levels_kernel(const float* __restrict__ x
                 }
             }
             tile[r][q] = v;
+            if constexpr (Src::kMap) Src::lds().depth[r][q] = dep;
         }
         __syncthreads();
         if (lev)
@@ -101,10 +161,15 @@ __global__ void __launch_bounds__(kRT) levels_kernel(const float* __restrict__ x
                 const int q = e / kLB, r = e - q * kLB;
                 if (b0 + r < n && q < ns) lev[(size_t)(s0 + q) * n + b0 + r] = tile[r][q];
             }
-        if (t < kLB)
+        if (t < kLB) {
             for (int q = 0; q < ns; ++q) sum += tile[t][q];
+            if constexpr (Src::kMap)
+                for (int q = 0; q < ns; ++q) dsum += Src::lds().depth[t][q];
+        }
     }
     if (level_mean && t < kLB && b0 + t < n) level_mean[b0 + t] = sum / (double)S;
+    if constexpr (Src::kMap)
+        if (depth_mean && t < kLB && b0 + t < n) depth_mean[b0 + t] = dsum / (double)S;
     __syncthreads();
     if (lds_hist)
         for (int k = t; k < nbins; k += kRT)
@@ -291,6 +356,47 @@ __global__ void __launch_bounds__(kRT) lamina_kernel(const float* __restrict__ x
     }
 }
 
+// One workgroup per haploid locus on the staged maps: the signed depth of every copy in every
+// structure below the lamina of the structure's map, less the radius of the locus's first
+// copy, counted against the map's threshold.  side = +1 a nucleus map (contact towards
+// the outside), -1 a body map (contact towards its inside).
+__global__ void __launch_bounds__(kRT) map_lamina_kernel(const float* __restrict__ xyz, int S,
+                                                         const int* __restrict__ copy_ptr,
+                                                         const int* __restrict__ copy_idx,
+                                                         const float* __restrict__ radii,
+                                                         const ms::VolMapDev* __restrict__ maps,
+                                                         const int4* __restrict__ vox, const int* __restrict__ smap,
+                                                         const double* __restrict__ thr, int side,
+                                                         long long* __restrict__ counts) {
+    __shared__ int red[kRT / 64];
+    const int h = blockIdx.x, t = threadIdx.x;
+    const int p0 = copy_ptr[h], nc = copy_ptr[h + 1] - p0;
+    const double r = nc > 0 ? (double)radii[copy_idx[p0]] : 0.0;
+    int cnt = 0;
+#pragma unroll 1
+    for (int s = t; s < S; s += kRT) {
+        const int mi = smap ? smap[s] : 0;
+        const ms::VolMapDev m = maps[mi];
+        const double th = thr[mi];
+#pragma unroll 1
+        for (int k = 0; k < nc; ++k) {
+            const float* x = xyz + ((size_t)copy_idx[p0 + k] * S + s) * 3;
+            const float p[3] = {x[0], x[1], x[2]};
+            const double d = exp_map_depth(p, m, vox);
+            cnt += ((side > 0 ? d : -d) - r) <= th;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o, 64);
+    if ((t & 63) == 0) red[t >> 6] = cnt;
+    __syncthreads();
+    if (t == 0) {
+        long long tot = 0;
+        for (int w = 0; w < kRT / 64; ++w) tot += red[w];
+        counts[h] = tot;
+    }
+}
+
 // Average distance map.  One workgroup per 64x64 tile of haploid loci (upper-triangle
 // tiles), a 4x4 block of entries per thread.  The outer loops run over the copy ranks
 // (ka, kb): a pass streams the ka-th copies of the tile's rows and the kb-th copies of
@@ -447,46 +553,58 @@ int check_edges(igm_ctx* c, const char* fn, const char* what, const double* e, i
     return IGM_OK;
 }
 
-}  // namespace
+// the density and shell arguments shared by igm_report_levels and igm_report_map_levels
+struct LevelOutputs {
+    double* level_mean;
+    const double* density_edges;
+    int32_t nbins;
+    int64_t* density_counts;
+    int32_t nshell;
+    double* shell_mean;
+    const double* shell_edges;
+    int32_t hnbins;
+    int64_t* shell_hist;
+};
 
-extern "C" int igm_report_levels(igm_ctx* c, uint32_t flags, const float* xyz, int32_t nbead, int32_t nstruct,
-                                 const double* semiaxes, double* level_mean, const double* density_edges,
-                                 int32_t nbins, int64_t* density_counts, int32_t nshell, double* shell_mean,
-                                 const double* shell_edges, int32_t hnbins, int64_t* shell_hist) {
-    static const char* fn = "igm_report_levels";
-    if (!c) return IGM_E_INVALID;
-    if (nbead <= 0 || nstruct <= 0 || !xyz || !semiaxes)
-        return fail(c, IGM_E_INVALID, "%s: invalid arguments (nbead %d, nstruct %d, xyz %p, semiaxes %p)", fn, nbead,
-                    nstruct, (const void*)xyz, (const void*)semiaxes);
-    if (nbead > 65535) return fail(c, IGM_E_UNSUPPORTED, "%s: %d beads, at most 65535 supported", fn, nbead);
-    for (int k = 0; k < 3; ++k)
-        if (!std::isfinite(semiaxes[k]) || !(semiaxes[k] > 0.0))
-            return fail(c, IGM_E_INVALID, "%s: semiaxes[%d] = %g is not a positive finite number", fn, k, semiaxes[k]);
-    if (density_counts) {
-        if (nbins < 1 || !density_edges)
-            return fail(c, IGM_E_INVALID, "%s: density_counts needs nbins >= 1 (%d) and nbins + 1 edges", fn, nbins);
-        IGM_TRY(check_edges(c, fn, "density_edges", density_edges, nbins));
+int check_level_outputs(igm_ctx* c, const char* fn, const LevelOutputs& o) {
+    if (o.density_counts) {
+        if (o.nbins < 1 || !o.density_edges)
+            return fail(c, IGM_E_INVALID, "%s: density_counts needs nbins >= 1 (%d) and nbins + 1 edges", fn, o.nbins);
+        IGM_TRY(check_edges(c, fn, "density_edges", o.density_edges, o.nbins));
     }
-    const bool shells = shell_mean || shell_hist;
-    if (shells) {
-        if (nshell < 1) return fail(c, IGM_E_INVALID, "%s: nshell = %d, expected >= 1", fn, nshell);
-        if (nshell > kMaxShell)
-            return fail(c, IGM_E_UNSUPPORTED, "%s: nshell = %d, at most %d supported", fn, nshell, kMaxShell);
-        if (shell_hist) {
-            if (hnbins < 1 || !shell_edges)
-                return fail(c, IGM_E_INVALID, "%s: shell_hist needs hnbins >= 1 (%d) and hnbins + 1 edges", fn, hnbins);
-            IGM_TRY(check_edges(c, fn, "shell_edges", shell_edges, hnbins));
+    if (o.shell_mean || o.shell_hist) {
+        if (o.nshell < 1) return fail(c, IGM_E_INVALID, "%s: nshell = %d, expected >= 1", fn, o.nshell);
+        if (o.nshell > kMaxShell)
+            return fail(c, IGM_E_UNSUPPORTED, "%s: nshell = %d, at most %d supported", fn, o.nshell, kMaxShell);
+        if (o.shell_hist) {
+            if (o.hnbins < 1 || !o.shell_edges)
+                return fail(c, IGM_E_INVALID, "%s: shell_hist needs hnbins >= 1 (%d) and hnbins + 1 edges", fn,
+                            o.hnbins);
+            IGM_TRY(check_edges(c, fn, "shell_edges", o.shell_edges, o.hnbins));
         }
     }
-    IGM_HIP_CHECK(c, hipSetDevice(c->device));
+    return IGM_OK;
+}
+
+// Both passes on checked arguments: the levels of `src` (its device pointers already
+// set), then the shells on the stored levels.  depth_mean: the map source's extra output.
+template <class Src>
+int run_levels(igm_ctx* c, uint32_t flags, const char* timer, const float* xyz, int32_t nbead, int32_t nstruct,
+               const Src& src, double* depth_mean, const LevelOutputs& o) {
+    double* const level_mean = o.level_mean;
+    int64_t *const density_counts = o.density_counts, *const shell_hist = o.shell_hist;
+    double* const shell_mean = o.shell_mean;
+    const int32_t nbins = o.nbins, nshell = o.nshell, hnbins = o.hnbins;
+    const bool shells = shell_mean || shell_hist;
     const float* d_xyz;
     IGM_TRY(to_device(c, flags, "rp_xyz", xyz, (size_t)nbead * nstruct * 3, &d_xyz));
     const double *d_edges = nullptr, *d_hedges = nullptr;
-    if (density_counts) IGM_TRY(to_device(c, 0u, "rp_edges", density_edges, (size_t)nbins + 1, &d_edges));
-    if (shell_hist) IGM_TRY(to_device(c, 0u, "rp_hedges", shell_edges, (size_t)hnbins + 1, &d_hedges));
-    double *d_mean, *d_smean;
+    if (density_counts) IGM_TRY(to_device(c, 0u, "rp_edges", o.density_edges, (size_t)nbins + 1, &d_edges));
+    if (shell_hist) IGM_TRY(to_device(c, 0u, "rp_hedges", o.shell_edges, (size_t)hnbins + 1, &d_hedges));
+    double *d_mean, *d_smean, *d_dmean;
     int64_t *d_dens, *d_shist;
     IGM_TRY(out_device(c, flags, "rp_mean", level_mean, (size_t)nbead, &d_mean));
+    IGM_TRY(out_device(c, flags, "rp_dmean", depth_mean, (size_t)nbead, &d_dmean));
     IGM_TRY(out_device(c, flags, "rp_dens", density_counts, (size_t)nbins, &d_dens));
     IGM_TRY(out_device(c, flags, "rp_smean", shell_mean, (size_t)nstruct * (shells ? nshell : 0), &d_smean));
     IGM_TRY(out_device(c, flags, "rp_shist", shell_hist, (size_t)(shells ? nshell : 0) * hnbins, &d_shist));
@@ -506,11 +624,11 @@ extern "C" int igm_report_levels(igm_ctx* c, uint32_t flags, const float* xyz, i
     if (density_counts) IGM_HIP_CHECK(c, hipMemsetAsync(d_dens, 0, sizeof(int64_t) * (size_t)nbins, c->stream));
     if (shell_hist) IGM_HIP_CHECK(c, hipMemsetAsync(d_shist, 0, sizeof(int64_t) * (size_t)nshell * hnbins, c->stream));
     {
-        Timed tm(c, "report_levels");
-        if (level_mean || density_counts || shells) {
-            hipLaunchKernelGGL(levels_kernel, dim3((unsigned)ceil_div(nbead, kLB)), dim3(kRT), 0, c->stream, d_xyz,
-                               (int)nbead, (int)nstruct, semiaxes[0], semiaxes[1], semiaxes[2], d_lev, d_mean, d_edges,
-                               (int)nbins, (u64*)d_dens);
+        Timed tm(c, timer);
+        if (level_mean || depth_mean || density_counts || shells) {
+            hipLaunchKernelGGL(levels_kernel<Src>, dim3((unsigned)ceil_div(nbead, kLB)), dim3(kRT), 0, c->stream, d_xyz,
+                               (int)nbead, (int)nstruct, src, d_lev, d_mean, d_dmean, d_edges, (int)nbins,
+                               (u64*)d_dens);
             IGM_HIP_CHECK(c, hipGetLastError());
         }
         if (shells) {
@@ -522,12 +640,100 @@ extern "C" int igm_report_levels(igm_ctx* c, uint32_t flags, const float* xyz, i
         }
     }
     IGM_TRY(to_host(c, flags, level_mean, d_mean, (size_t)nbead));
+    IGM_TRY(to_host(c, flags, depth_mean, d_dmean, (size_t)nbead));
     IGM_TRY(to_host(c, flags, density_counts, d_dens, (size_t)nbins));
     if (shells) {
         IGM_TRY(to_host(c, flags, shell_mean, d_smean, (size_t)nstruct * nshell));
         IGM_TRY(to_host(c, flags, shell_hist, d_shist, (size_t)nshell * hnbins));
     }
     return finish(c, flags);
+}
+
+// The staged maps and the map index of every structure of a call, on the device: smap is
+// the caller's struct_map (host, checked against the pool), else the table staged with the
+// maps (which must cover the call), else NULL for map 0 -- igm_volume_select's convention.
+struct StagedMaps {
+    const ms::VolMapDev* maps;
+    const int4* vox;
+    const int* smap;
+};
+
+int staged_maps(igm_ctx* c, const char* fn, const int32_t* struct_map, int32_t nstruct, StagedMaps* out) {
+    if (c->vol_nmap <= 0) return fail(c, IGM_E_INVALID, "%s: no map staged (igm_mstep_set_volumes)", fn);
+    if (struct_map) {
+        for (int s = 0; s < nstruct; ++s)
+            if (struct_map[s] < 0 || struct_map[s] >= c->vol_nmap)
+                return fail(c, IGM_E_INVALID, "%s: struct_map[%d] = %d outside [0, %d)", fn, s, struct_map[s],
+                            c->vol_nmap);
+    } else if (c->vol_nsmap > 0 && c->vol_nsmap < nstruct) {
+        return fail(c, IGM_E_INVALID, "%s: volume map index staged for %d structures, batch has %d", fn, c->vol_nsmap,
+                    nstruct);
+    }
+    IGM_HIP_CHECK(c, hipSetDevice(c->device));
+    void *pm, *pv, *ps;
+    IGM_TRY(workspace(c, "vol_maps", 1, &pm));
+    IGM_TRY(workspace(c, "vol_vox", 1, &pv));
+    out->maps = (const ms::VolMapDev*)pm;
+    out->vox = (const int4*)pv;
+    out->smap = nullptr;
+    if (struct_map) {
+        IGM_TRY(to_device(c, 0u, "rp_smap", struct_map, (size_t)nstruct, &out->smap));
+    } else if (c->vol_nsmap > 0) {
+        IGM_TRY(workspace(c, "vol_smap", 1, &ps));
+        out->smap = (const int*)ps;
+    }
+    return IGM_OK;
+}
+
+}  // namespace
+
+extern "C" int igm_report_levels(igm_ctx* c, uint32_t flags, const float* xyz, int32_t nbead, int32_t nstruct,
+                                 const double* semiaxes, double* level_mean, const double* density_edges,
+                                 int32_t nbins, int64_t* density_counts, int32_t nshell, double* shell_mean,
+                                 const double* shell_edges, int32_t hnbins, int64_t* shell_hist) {
+    static const char* fn = "igm_report_levels";
+    if (!c) return IGM_E_INVALID;
+    if (nbead <= 0 || nstruct <= 0 || !xyz || !semiaxes)
+        return fail(c, IGM_E_INVALID, "%s: invalid arguments (nbead %d, nstruct %d, xyz %p, semiaxes %p)", fn, nbead,
+                    nstruct, (const void*)xyz, (const void*)semiaxes);
+    if (nbead > 65535) return fail(c, IGM_E_UNSUPPORTED, "%s: %d beads, at most 65535 supported", fn, nbead);
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(semiaxes[k]) || !(semiaxes[k] > 0.0))
+            return fail(c, IGM_E_INVALID, "%s: semiaxes[%d] = %g is not a positive finite number", fn, k, semiaxes[k]);
+    const LevelOutputs o{level_mean, density_edges, nbins, density_counts, nshell, shell_mean, shell_edges, hnbins,
+                         shell_hist};
+    IGM_TRY(check_level_outputs(c, fn, o));
+    IGM_HIP_CHECK(c, hipSetDevice(c->device));
+    const EllipsoidLevels src{semiaxes[0], semiaxes[1], semiaxes[2]};
+    return run_levels(c, flags, "report_levels", xyz, nbead, nstruct, src, nullptr, o);
+}
+
+extern "C" int igm_report_map_levels(igm_ctx* c, uint32_t flags, const float* xyz, int32_t nbead, int32_t nstruct,
+                                     const int32_t* struct_map, const double* depth_scale, double* level_mean,
+                                     double* depth_mean, const double* density_edges, int32_t nbins,
+                                     int64_t* density_counts, int32_t nshell, double* shell_mean,
+                                     const double* shell_edges, int32_t hnbins, int64_t* shell_hist) {
+    static const char* fn = "igm_report_map_levels";
+    if (!c) return IGM_E_INVALID;
+    if (nbead <= 0 || nstruct <= 0 || !xyz || !depth_scale)
+        return fail(c, IGM_E_INVALID, "%s: invalid arguments (nbead %d, nstruct %d, xyz %p, depth_scale %p)", fn, nbead,
+                    nstruct, (const void*)xyz, (const void*)depth_scale);
+    if (nbead > 65535) return fail(c, IGM_E_UNSUPPORTED, "%s: %d beads, at most 65535 supported", fn, nbead);
+    for (int m = 0; m < c->vol_nmap; ++m)
+        if (!std::isfinite(depth_scale[m]) || !(depth_scale[m] > 0.0))
+            return fail(c, IGM_E_INVALID, "%s: depth_scale[%d] = %g is not a positive finite number", fn, m,
+                        depth_scale[m]);
+    const LevelOutputs o{level_mean, density_edges, nbins, density_counts, nshell, shell_mean, shell_edges, hnbins,
+                         shell_hist};
+    IGM_TRY(check_level_outputs(c, fn, o));
+    StagedMaps sm;
+    IGM_TRY(staged_maps(c, fn, struct_map, nstruct, &sm));
+    const double* d_scale;
+    IGM_TRY(to_device(c, 0u, "rp_scale", depth_scale, (size_t)c->vol_nmap, &d_scale));
+    // struct_map and depth_scale are the caller's and were copied asynchronously: wait before going on
+    IGM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    const MapLevels src{sm.maps, sm.vox, sm.smap, d_scale};
+    return run_levels(c, flags, "report_map_levels", xyz, nbead, nstruct, src, depth_mean, o);
 }
 
 extern "C" int igm_report_rg(igm_ctx* c, uint32_t flags, const float* xyz, int32_t nbead, int32_t nstruct,
@@ -589,6 +795,42 @@ extern "C" int igm_report_lamina(igm_ctx* c, uint32_t flags, const float* xyz, i
         IGM_HIP_CHECK(c, hipGetLastError());
     }
     IGM_TRY(to_host(c, flags, counts, d_cnt, (size_t)nhap));
+    IGM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    return finish(c, flags);
+}
+
+extern "C" int igm_report_map_lamina(igm_ctx* c, uint32_t flags, const float* xyz, int32_t nbead, int32_t nstruct,
+                                     const int32_t* copy_ptr, const int32_t* copy_idx, int32_t nhap,
+                                     const float* radii, const int32_t* struct_map, const double* thr, int32_t side,
+                                     int64_t* counts) {
+    static const char* fn = "igm_report_map_lamina";
+    if (!c) return IGM_E_INVALID;
+    if (nbead <= 0 || nstruct <= 0 || nhap <= 0 || !xyz || !copy_ptr || !copy_idx || !radii || !thr || !counts)
+        return fail(c, IGM_E_INVALID, "%s: invalid arguments (nbead %d, nstruct %d, nhap %d)", fn, nbead, nstruct, nhap);
+    if (side != 1 && side != -1) return fail(c, IGM_E_INVALID, "%s: side = %d, expected +1 or -1", fn, side);
+    IGM_TRY(check_csr(c, fn, "copy", copy_ptr, copy_idx, nhap, nbead, nullptr));
+    for (int m = 0; m < c->vol_nmap; ++m)
+        if (!std::isfinite(thr[m])) return fail(c, IGM_E_INVALID, "%s: thr[%d] = %g is not finite", fn, m, thr[m]);
+    StagedMaps sm;
+    IGM_TRY(staged_maps(c, fn, struct_map, nstruct, &sm));
+    const float *d_xyz, *d_radii;
+    const int32_t *d_ptr, *d_idx;
+    const double* d_thr;
+    IGM_TRY(to_device(c, flags, "rp_xyz", xyz, (size_t)nbead * nstruct * 3, &d_xyz));
+    IGM_TRY(to_device(c, 0u, "rp_cptr", copy_ptr, (size_t)nhap + 1, &d_ptr));
+    IGM_TRY(to_device(c, 0u, "rp_cidx", copy_idx, (size_t)copy_ptr[nhap], &d_idx));
+    IGM_TRY(to_device(c, 0u, "rp_radii", radii, (size_t)nbead, &d_radii));
+    IGM_TRY(to_device(c, 0u, "rp_thr", thr, (size_t)c->vol_nmap, &d_thr));
+    int64_t* d_cnt;
+    IGM_TRY(out_device(c, flags, "rp_lam", counts, (size_t)nhap, &d_cnt));
+    {
+        Timed tm(c, "report_map_lamina");
+        hipLaunchKernelGGL(map_lamina_kernel, dim3((unsigned)nhap), dim3(kRT), 0, c->stream, d_xyz, (int)nstruct, d_ptr,
+                           d_idx, d_radii, sm.maps, sm.vox, sm.smap, d_thr, (int)side, (long long*)d_cnt);
+        IGM_HIP_CHECK(c, hipGetLastError());
+    }
+    IGM_TRY(to_host(c, flags, counts, d_cnt, (size_t)nhap));
+    // the host arrays are the caller's and were copied asynchronously: wait before returning
     IGM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
     return finish(c, flags);
 }

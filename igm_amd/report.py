@@ -16,6 +16,10 @@ bin/igm-report) computed on the GPU from the bead-major population.
                           the input Hi-C matrix and the simulated contact map, per chromosome
                           and inter-chromosomal, over all / imposed / non-imposed entries, and
                           the two 2-D histograms of plots.py, igm_report_hic
+  map_levels / map_density / map_shells / map_lamina_frequency
+                       -- the same numbers inside an imaged nucleus (nucleus_shape exp_map), on
+                          the level below the lamina of every structure's map (this project's
+                          definitions, include/igm_hip.h: igm_report_map_levels / _map_lamina)
   report_population    -- the numeric files bin/igm-report leaves in its output directory
                           (names and formats of the reference); plots, images and the HTML
                           page stay with the reference
@@ -39,6 +43,7 @@ from . import _lib
 
 STEPS = ('rgs', 'shells', 'radials', 'damid', 'distance_map')
 OPTIONAL_STEPS = ('hic',)                    # accepted in `steps`, not run by default
+BODY_STEPS = ('bodies',)                     # optional too: the nuclear bodies of an imaged nucleus
 DEFAULT_SEMIAXES = (5000.0, 5000.0, 5000.0)  # report_radials / report_shells / report_damid
 DEFAULT_DAMID_CONTACT_RANGE = 0.05           # restraints/DamID/contact_range of the reference's config defaults
 
@@ -227,6 +232,163 @@ def lamina_frequency(pop, radii=None, copy_ptr=None, copy_idx=None, semiaxes=Non
     xyz, store = _population(pop)
     counts, ncopy = lamina_counts(xyz if store is None else store, radii, copy_ptr, copy_idx, semiaxes, contact_range,
                                   ctx=ctx, device=device)
+    return counts.astype(np.float64) / xyz.shape[1] / ncopy
+
+
+# ------------------------------------------------------------------ imaged nuclei (exp_map)
+def _inside_depths(vol):
+    """|(v - e) * grid| in float64 of every voxel with w != 0, summed (t0^2 + t2^2) + t1^2"""
+    mat = np.asarray(vol['matrice'])
+    inside = mat[..., 3] != 0
+    v = np.stack(np.nonzero(inside), axis=1).astype(np.int64)
+    t = (v - mat[inside][:, :3].astype(np.int64)).astype(np.float64) * np.asarray(vol['grid'], np.float32).astype(
+        np.float64)
+    t = t * t
+    return np.sqrt((t[:, 0] + t[:, 2]) + t[:, 1])
+
+
+def map_depth_scale(vol):
+    """The depth scale of a map: the largest voxel-centre depth |(v - e) * grid| over the
+    voxels with w != 0, float64.  ValueError for a map without an inside voxel or whose
+    inside voxels are all lamina voxels (scale 0)."""
+    d = _inside_depths(vol)
+    if d.size == 0:
+        raise ValueError('the map has no inside voxel')
+    dmax = float(d.max())
+    if not (np.isfinite(dmax) and dmax > 0):
+        raise ValueError('the map has no voxel below its lamina (depth scale %r)' % dmax)
+    return dmax
+
+
+def map_shell_volumes(vol, edges, depth_scale=None):
+    """V[k]: the voxel volume times the number of inside voxels whose centre level
+    1 - |(v - e) grid| / depth_scale falls in bin k of np.histogram on `edges`"""
+    dmax = map_depth_scale(vol) if depth_scale is None else float(depth_scale)
+    lev = 1 - _inside_depths(vol) / dmax
+    g = np.asarray(vol['grid'], np.float32).astype(np.float64)
+    return np.histogram(lev, bins=np.asarray(edges, np.float64))[0] * (g[0] * g[1] * g[2])
+
+
+def _stage_maps(c, volumes, struct_map, nstruct):
+    """the maps and the per-structure index staged on the context (volume.stage), as the
+    DamID A-step's exp_map wrapper does: (nmap, depth scales)"""
+    from . import volume as V
+    if volumes is None or len(volumes) == 0:
+        raise ValueError('the map forms need the volume maps')
+    if struct_map is not None:
+        struct_map = np.ascontiguousarray(struct_map, np.int32)
+        if struct_map.shape != (nstruct,) or struct_map.min() < 0 or struct_map.max() >= len(volumes):
+            raise ValueError('struct_map must name one of the %d maps for each of the %d structures'
+                             % (len(volumes), nstruct))
+    scale = np.array([map_depth_scale(v) for v in volumes], np.float64)
+    V.stage(c, volumes, struct_map)
+    return scale
+
+
+def _map_levels(xyz, volumes, struct_map, ctx, device, want_mean=False, want_depth=False, density_edges=None, nshell=0,
+                shell_edges=None):
+    """igm_report_map_levels on freshly staged maps: (level_mean, depth_mean, density,
+    shell_mean, shell_hist), None where not asked for"""
+    nbead, S = xyz.shape[0], xyz.shape[1]
+    c = ctx or _lib.context(device)
+    scale = _stage_maps(c, volumes, struct_map, S)
+    mean = np.empty(nbead, np.float64) if want_mean else None
+    depth = np.empty(nbead, np.float64) if want_depth else None
+    dens = de = None
+    if density_edges is not None:
+        de = np.ascontiguousarray(density_edges, np.float64)
+        dens = np.empty(len(de) - 1, np.int64)
+    smean = shist = se = None
+    if nshell:
+        se = np.ascontiguousarray(shell_edges, np.float64)
+        smean = np.empty((S, nshell), np.float64)
+        shist = np.empty((nshell, len(se) - 1), np.int64)
+    rc = c.lib.igm_report_map_levels(c.h, 0, xyz.ctypes.data, nbead, S, None, scale.ctypes.data, _lib.ptr(mean),
+                                     _lib.ptr(depth), _lib.ptr(de), 0 if de is None else len(de) - 1, _lib.ptr(dens),
+                                     int(nshell), _lib.ptr(smean), _lib.ptr(se), 0 if se is None else len(se) - 1,
+                                     _lib.ptr(shist))
+    c.check(rc, 'igm_report_map_levels')
+    return mean, depth, dens, smean, shist
+
+
+def map_levels(pop, volumes, struct_map=None, copy_ptr=None, copy_idx=None, ctx=None, device=0):
+    """(level means, mean signed depths) of every bead on the maps of an imaged nucleus:
+    volumes are volume.read_volume dicts and struct_map[s] the map of structure s (None:
+    map 0).  The level is max(0, 1 - depth / map_depth_scale): 1 on the lamina, 0 on the
+    deepest voxel centre.  With a copy index (or a PopulationStore) the copies are averaged
+    like radial_levels does: (nhap,) each."""
+    xyz, store = _population(pop)
+    mean, depth = _map_levels(xyz, volumes, struct_map, ctx, device, want_mean=True, want_depth=True)[:2]
+    if store is not None and copy_ptr is None:
+        copy_ptr, copy_idx = store.copy_ptr, store.copy_idx
+    if copy_ptr is None:
+        return mean, depth
+    copy_ptr, copy_idx = _csr(copy_ptr, copy_idx, xyz.shape[0], 'copy')
+    return average_copies(mean, copy_ptr, copy_idx), average_copies(depth, copy_ptr, copy_idx)
+
+
+def map_density(pop, volumes, struct_map=None, n=11, vmax=1.1, ctx=None, device=0):
+    """(counts (n,) int64, edges, volumes (n,)) of the map levels: np.histogram over all
+    nbead * nstruct levels, and the real shell volume behind every bin summed over the
+    structures, sum_s V_map(s)[k] (map_shell_volumes)"""
+    xyz, _ = _population(pop)
+    if n < 1 or not vmax > 0:
+        raise ValueError('map_density needs n >= 1 bins and vmax > 0')
+    edges = np.linspace(0, vmax, n + 1)
+    counts = _map_levels(xyz, volumes, struct_map, ctx, device, density_edges=edges)[2]
+    S = xyz.shape[1]
+    smap = np.zeros(S, np.int64) if struct_map is None else np.asarray(struct_map, np.int64)
+    per_map = np.bincount(smap, minlength=len(volumes)).astype(np.float64)
+    vols = np.zeros(n)
+    for m, v in enumerate(volumes):
+        if per_map[m]:
+            vols += per_map[m] * map_shell_volumes(v, edges)
+    return counts, edges, vols
+
+
+def map_shells(pop, volumes, struct_map=None, nshell=5, hvmax=1.5, hnbins=150, ctx=None, device=0):
+    """shells() on the map levels: (shell_mean (nstruct, nshell), shell_hist, edges)"""
+    xyz, _ = _population(pop)
+    if nshell < 1 or hnbins < 1 or not hvmax > 0:
+        raise ValueError('map_shells needs nshell >= 1, hnbins >= 1 and hvmax > 0')
+    edges = np.linspace(0, hvmax, hnbins + 1)
+    _, _, _, smean, shist = _map_levels(xyz, volumes, struct_map, ctx, device, nshell=nshell, shell_edges=edges)
+    return smean, shist, edges
+
+
+def map_lamina_counts(pop, volumes, struct_map=None, radii=None, copy_ptr=None, copy_idx=None, contact_range=0.05,
+                      side=1, ctx=None, device=0):
+    """(counts (nhap,) int64, copies (nhap,)): the (copy, structure) pairs in contact with
+    the lamina of their structure's map, depth - r <= contact_range * map_depth_scale with r
+    the radius of the locus's first copy; side = -1 for a body map (a nucleolus, whose w
+    marks the inside of the body): -depth - r <= contact_range * map_depth_scale."""
+    xyz, store = _population(pop)
+    radii = np.ascontiguousarray(_pick(radii, store, 'radii'), np.float32)
+    copy_ptr, copy_idx = _csr(_pick(copy_ptr, store, 'copy_ptr'), _pick(copy_idx, store, 'copy_idx'), xyz.shape[0],
+                              'copy')
+    if len(radii) != xyz.shape[0]:
+        raise ValueError('radii must have one entry per bead')
+    if np.any(np.diff(copy_ptr) < 1):
+        raise ValueError('every haploid locus needs at least one copy')
+    if side not in (1, -1):
+        raise ValueError('side is +1 (a nucleus map) or -1 (a body map)')
+    c = ctx or _lib.context(device)
+    thr = np.ascontiguousarray(float(contact_range) * _stage_maps(c, volumes, struct_map, xyz.shape[1]))
+    nhap = len(copy_ptr) - 1
+    out = np.empty(nhap, np.int64)
+    rc = c.lib.igm_report_map_lamina(c.h, 0, xyz.ctypes.data, xyz.shape[0], xyz.shape[1], copy_ptr.ctypes.data,
+                                     copy_idx.ctypes.data, nhap, radii.ctypes.data, None, thr.ctypes.data, int(side),
+                                     out.ctypes.data)
+    c.check(rc, 'igm_report_map_lamina')
+    return out, np.diff(copy_ptr)
+
+
+def map_lamina_frequency(pop, volumes, struct_map=None, radii=None, copy_ptr=None, copy_idx=None, contact_range=0.05,
+                         side=1, ctx=None, device=0):
+    """lamina_frequency on the maps: float(count) / nstruct / n_copies, (nhap,) float64"""
+    xyz, store = _population(pop)
+    counts, ncopy = map_lamina_counts(xyz if store is None else store, volumes, struct_map, radii, copy_ptr, copy_idx,
+                                      contact_range, side, ctx=ctx, device=device)
     return counts.astype(np.float64) / xyz.shape[1] / ncopy
 
 
@@ -505,6 +667,21 @@ def _hss_extras(path):
     return shape, params, chroms, config
 
 
+def named_maps(cfg, nstruct):
+    """(volumes, struct_map) of an exp_map configuration that itself names its maps --
+    model/restraints/envelope/volume_prefix and volumes_idx present as raw keys, not through
+    the schema defaults ('' and [0]) -- else None.  The files are those of
+    steps.envelope_section(cfg, range(nstruct))."""
+    env = _cfg_get(cfg, 'model/restraints/envelope')
+    if not isinstance(env, dict) or 'volume_prefix' not in env or 'volumes_idx' not in env:
+        return None
+    if env.get('nucleus_shape') != 'exp_map':
+        return None
+    from .steps import envelope_section
+    sec = envelope_section(cfg, range(nstruct))
+    return sec['volumes'], sec['struct_map']
+
+
 def resolve_semiaxes(hss_envelope, cfg_params, explicit=None):
     """The semiaxes of the radial, shell and lamina numbers, or None when the nucleus is an
     exp_map and none were given.  Order: the caller's explicit semiaxes; envelope/params
@@ -545,8 +722,15 @@ def report_population(hss_path, cfg=None, out_dir=None, steps=STEPS, label='', s
 
     cfg: an IGM configuration (dict or JSON file); None looks for config_data in the .hss,
     then for igm-config.json beside it (bin/igm-report:236-262).  steps: any of STEPS, and
-    'hic' (not run by default).  radials, shells and damid need semiaxes (resolve_semiaxes)
-    and raise ValueError on an exp_map nucleus without explicit ones.  hic needs the Hi-C
+    'hic' and 'bodies' (not run by default).  radials, shells and damid need semiaxes
+    (resolve_semiaxes).  On an exp_map nucleus without explicit ones they run in their map
+    forms when the configuration names its maps (named_maps): the same file names hold the
+    levels below the lamina, density_histo.txt is divided by the real shell volumes (nan for
+    a bin without volume) and radials/lamina_depth.txt holds the mean signed depth per
+    haploid locus; a configuration that names no maps raises ValueError.  bodies needs
+    model/restraints/nucleolus and writes bodies/nucleolus_frequency.txt (contacts at
+    restraints/nuclDamID/contact_range, else the DamID default) and
+    bodies/nucleolus_distance.txt (the mean of -depth).  hic needs the Hi-C
     section of the configuration or the hic argument (the path of the input .hcs; the
     hic_* arguments are the command line's, apply_hic_arguments) and raises ValueError
     without one (the reference only logs).  It writes matrix_comparison/outmap.hcs,
@@ -556,9 +740,10 @@ def report_population(hss_path, cfg=None, out_dir=None, steps=STEPS, label='', s
     are nan (the reference then writes no intra rows and zeros in the inter row)."""
     from .steps import PopulationStore
     steps = tuple(steps.split(',')) if isinstance(steps, str) else tuple(steps)
-    unknown = [s for s in steps if s not in STEPS + OPTIONAL_STEPS]
+    known = STEPS + OPTIONAL_STEPS + BODY_STEPS
+    unknown = [s for s in steps if s not in known]
     if unknown:
-        raise ValueError('unknown report steps %s (known: %s)' % (unknown, ', '.join(STEPS + OPTIONAL_STEPS)))
+        raise ValueError('unknown report steps %s (known: %s)' % (unknown, ', '.join(known)))
     hss_path = os.path.realpath(hss_path)
     store = PopulationStore(hss_path)
     env_shape = env_params = chrom_names = stored = None
@@ -587,9 +772,24 @@ def report_population(hss_path, cfg=None, out_dir=None, steps=STEPS, label='', s
                              '--hic-contact-range')
     sx = resolve_semiaxes((env_shape, env_params), params, semiaxes)
     needs = [s for s in steps if s in ('radials', 'shells', 'damid')]
+    maps = None
     if sx is None and needs:
-        raise ValueError('the nucleus is an exp_map (no ellipsoid): the steps %s need explicit semiaxes'
-                         % ', '.join(needs))
+        maps = named_maps(cfg, store.nstruct)
+        if maps is None:
+            raise ValueError('the nucleus is an exp_map (no ellipsoid) and the configuration names no maps '
+                             '(model/restraints/envelope/volume_prefix and volumes_idx): the steps %s need explicit '
+                             'semiaxes' % ', '.join(needs))
+        for v in maps[0]:
+            map_depth_scale(v)  # a map without depth raises here, before anything is written
+    bodies = None
+    if 'bodies' in steps:
+        if not isinstance(_cfg_get(cfg, 'model/restraints/nucleolus'), dict):
+            raise ValueError('the bodies step needs model/restraints/nucleolus in the configuration')
+        from .steps import nucleolus_section
+        sec = nucleolus_section(cfg, range(store.nstruct))
+        bodies = (sec['volumes'], sec['struct_map'])
+        for v in bodies[0]:
+            map_depth_scale(v)
     if out_dir is None:
         base = os.path.splitext(os.path.basename(hss_path))[0]
         out_dir = os.path.join(os.path.dirname(hss_path), 'QC_' + (label or base))
@@ -614,26 +814,45 @@ def report_population(hss_path, cfg=None, out_dir=None, steps=STEPS, label='', s
             ['chr%d' % (i + 1) for i in ids]
         np.savez(path('radius_of_gyration/chromosomes%s.npz' % tag), **{c: a for c, a in zip(names, rgs)})
     if 'shells' in steps:
-        smean, _, _ = shells(xyz, sx, **kw)
+        if maps is None:
+            smean, _, _ = shells(xyz, sx, **kw)
+        else:
+            smean, _, _ = map_shells(xyz, maps[0], maps[1], **kw)
         np.savetxt(path('shells/ave_radial%s.txt' % tag), np.average(smean, axis=0))
     if 'radials' in steps:
-        radials = radial_levels(xyz, sx, store.copy_ptr, store.copy_idx, **kw)
+        if maps is None:
+            radials = radial_levels(xyz, sx, store.copy_ptr, store.copy_idx, **kw)
+            counts, edges = radial_density(xyz, sx, **kw)
+            volumes = np.array([edges[i + 1]**3 - edges[i]**3 for i in range(len(counts))])
+        else:  # an imaged nucleus: the level below the map's lamina and the real shell volumes
+            radials, depth = map_levels(xyz, maps[0], maps[1], store.copy_ptr, store.copy_idx, **kw)
+            np.savetxt(path('radials/lamina_depth%s.txt' % tag), depth)
+            counts, edges, volumes = map_density(xyz, maps[0], maps[1], **kw)
+            volumes = np.where(volumes > 0, volumes, np.nan)  # a bin without volume is nan
         np.savetxt(path('radials/radials%s.txt' % tag), radials)
-        counts, edges = radial_density(xyz, sx, **kw)
-        volumes = np.array([edges[i + 1]**3 - edges[i]**3 for i in range(len(counts))])
         np.savetxt(path('radials/density_histo%s.txt' % tag), counts / volumes)
         ave = os.path.join(out_dir, 'shells/ave_radial%s.txt' % tag)
         if os.path.isfile(ave):  # normalised with respect to the last shell (report_radials:119-122)
             np.savetxt(path('radials/radials_norm%s.txt' % tag), radials / np.loadtxt(ave)[-1])
     if 'damid' in steps:
         dcfg = params.get('damid') or {}
-        freq = lamina_frequency(xyz, store.radii, store.copy_ptr, store.copy_idx, sx,
-                                dcfg.get('contact_range', DEFAULT_DAMID_CONTACT_RANGE), **kw)
+        cr = dcfg.get('contact_range', DEFAULT_DAMID_CONTACT_RANGE)
+        if maps is None:
+            freq = lamina_frequency(xyz, store.radii, store.copy_ptr, store.copy_idx, sx, cr, **kw)
+        else:
+            freq = map_lamina_frequency(xyz, maps[0], maps[1], store.radii, store.copy_ptr, store.copy_idx, cr, **kw)
         np.savetxt(path('damid/output.txt'), freq)
         if dcfg.get('input_profile'):
             profile = np.loadtxt(dcfg['input_profile'], dtype='float32')
             np.savetxt(path('damid/input%s.txt' % tag), profile)
             np.savetxt(path('damid/pearsonr%s.txt' % tag), pearson(profile, freq))
+    if 'bodies' in steps:  # the nucleolus: contacts towards the inside of the body, distance = -depth
+        cr = _cfg_get(cfg, 'restraints/nuclDamID/contact_range', DEFAULT_DAMID_CONTACT_RANGE)
+        np.savetxt(path('bodies/nucleolus_frequency%s.txt' % tag),
+                   map_lamina_frequency(xyz, bodies[0], bodies[1], store.radii, store.copy_ptr, store.copy_idx, cr,
+                                        side=-1, **kw))
+        _, depth = map_levels(xyz, bodies[0], bodies[1], store.copy_ptr, store.copy_idx, **kw)
+        np.savetxt(path('bodies/nucleolus_distance%s.txt' % tag), -depth)
     if 'distance_map' in steps:
         np.save(path('distance_map/average%s.npy' % tag),
                 average_distance_map(xyz, store.copy_ptr, store.copy_idx, store.hap_chrom, **kw))

@@ -609,6 +609,65 @@ int igm_report_lamina(igm_ctx* ctx, uint32_t flags,
                       const int32_t* copy_ptr, const int32_t* copy_idx, int32_t nhap,
                       const double* inv_denoms, int64_t* counts);
 
+/* ---- the report on an imaged nucleus (nucleus_shape exp_map) ---------------------------
+ * The reference has no report for imaged nuclei (its get_damid_actdist_exp counts
+ * d_sq >= contact_range on sorted squared distances, which is no contact test): the
+ * definitions are this project's, chosen so that on a voxelised sphere they reduce to the
+ * ellipsoid forms above up to the voxel size.  Both entries read the maps staged by
+ * igm_mstep_set_volumes.  struct_map (nstruct) names the map of every structure; NULL
+ * means the table staged with the maps, and map 0 when none was staged (the convention
+ * of igm_volume_select).  struct_map, depth_scale, thr, radii and the CSR arrays are host
+ * pointers in every mode; xyz and the outputs follow `flags`.  Everything is float64 on
+ * the widened float32 coordinates and the widened float32 map geometry.  For a bead p
+ * and the map m of its structure:
+ *   voxel    v_d = rint((f64 p_d - f64 origin_d) / f64 grid_d), half to even, as the DamID
+ *            A-step reads it.  Out of the grid v is clamped to [0, n_d - 1] per axis and
+ *            the bead counts as outside.
+ *   record   (i, j, k, w) = the voxel record at ((v0 n1 + v1) n2 + v2);
+ *            L_d = f64(e_d) * grid_d + origin_d, e = (i, j, k); t = p - L;
+ *            dist = sqrt((t0^2 + t2^2) + t1^2), correctly rounded
+ *   depth    +dist when the voxel is in the grid and w != 0, else -dist: positive inside
+ *            the nucleus, 0 on a lamina voxel's centre, negative outside
+ *   level    max(0, 1 - depth / depth_scale[m]): 1 on the lamina, 0 on the deepest voxel
+ *            centre when depth_scale[m] is the largest |(v - e) * grid| over the voxels
+ *            with w != 0 (igm_amd.report.map_depth_scale), above 1 outside.  The clamp is
+ *            required: a bead off the centre of a deep voxel has depth > depth_scale, and
+ *            the shells are selected on the bit patterns of non-negative doubles.  The
+ *            sign bit of a level is clear.
+ * IGM_E_INVALID: no maps staged, a struct_map entry outside [0, nmap), a staged table
+ * shorter than nstruct, a depth_scale that is not finite and positive, a non-finite thr,
+ * side not +1 / -1.  The context stays usable. */
+
+/* Levels on the maps: the outputs of igm_report_levels -- same semantics, limits
+ * (nbead <= 65535, nshell <= 256: IGM_E_UNSUPPORTED) and NULL rules -- on the level above,
+ * and
+ *   depth_mean     (nbead) f64: the mean signed depth over the structures (summed in
+ *                  structure order); may be NULL
+ * depth_scale (nmap) f64, one per staged map. */
+int igm_report_map_levels(igm_ctx* ctx, uint32_t flags,
+                          const float* xyz, int32_t nbead, int32_t nstruct,
+                          const int32_t* struct_map, const double* depth_scale,
+                          double* level_mean, double* depth_mean,
+                          const double* density_edges, int32_t nbins, int64_t* density_counts,
+                          int32_t nshell, double* shell_mean,
+                          const double* shell_edges, int32_t hnbins, int64_t* shell_hist);
+
+/* Contacts with the lamina of the maps, the shape of igm_report_lamina: counts (nhap)
+ * int64 = the number of (copy, structure) in contact.  radii (nbead) f32; r is the radius
+ * of the locus's FIRST copy, as in igm_report_lamina.  thr (nmap) f64, formed by the
+ * caller as contact_range * depth_scale[m].
+ *   side = +1  a nucleus map: contact iff depth - f64(r) <= thr[m].  On a sphere this is
+ *              the ellipsoid form, |x| >= R (1 - cr) - r  <=>  (R - |x|) - r <= cr R.
+ *              Every outside bead is in contact.
+ *   side = -1  a body map (a nucleolus; w marks the inside of the body): contact iff
+ *              -depth - f64(r) <= thr[m].
+ * A locus without copies counts 0. */
+int igm_report_map_lamina(igm_ctx* ctx, uint32_t flags,
+                          const float* xyz, int32_t nbead, int32_t nstruct,
+                          const int32_t* copy_ptr, const int32_t* copy_idx, int32_t nhap,
+                          const float* radii, const int32_t* struct_map, const double* thr,
+                          int32_t side, int64_t* counts);
+
 /* Average distance map: create_average_distance_map (igm/report/distance_map.py:5-22).
  * dmap (nhap, nhap) f64.  For a copy pair (k, m) the float32 norms
  * sqrt((dx*dx + dy*dy) + dz*dz) (np.linalg.norm(axis=1) on float32) are averaged over
