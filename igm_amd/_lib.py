@@ -155,6 +155,8 @@ SIGNATURES = {
     'igm_report_distance_map': (_i32, [_vp, _u32, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp]),
     'igm_report_hic': (_i32, [_vp, _u32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _f64, _f64,
                               _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'igm_report_neighbours': (_i32, [_vp, _u32, _vp, _i32, _i32, _vp, _vp, _i32, _i32, ctypes.c_float, _vp, _f64,
+                                     _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

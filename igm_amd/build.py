@@ -34,6 +34,8 @@ SOURCES = {
     # the report restates NumPy f32 / f64 arithmetic; its f32 sqrt stays correctly rounded
     'report.hip': ['-ffp-contract=off'],
     'report_hic.hip': ['-ffp-contract=off'],
+    # the neighbour census decides the contact map's float32 test: no FMAs either
+    'report_neighbours.hip': ['-ffp-contract=off'],
     # fp64 sums and a Jacobi eigenvalue: nothing is restated bit for bit, FMAs are welcome
     'tracing_assign.hip': [],
     'tracing_cells.hip': [],

@@ -1678,26 +1678,13 @@ extern "C" int igm_polymer_assign(igm_ctx* c, uint32_t flags, const float* xyz, 
 // before summing the copies.  counts[i, j] = the number of structures with
 // |x_i - x_j| <= fl32(contact_range * fl32(r_i + r_j)), the float32 norm of the A/M
 // contact test (inter_hic.py:47) against the Hi-C restraint's r0 (hic.py), decided
-// exactly on the squared norm (sq_bound).  One
+// exactly on the squared norm (sq_bound of exact_math.h).  One
 // workgroup per 64x64 bead tile (upper triangle, mirrored on store); the structures
 // stream through LDS in chunks of kCS, each thread keeps a 4x4 block of counters.
 namespace {
 constexpr int kCT = 64;  // beads per tile side
 constexpr int kCS = 32;  // structures per LDS chunk
 constexpr int kCRow = kCS * 3 + 1;  // padded LDS row (floats)
-
-// The largest float T with  RN(sqrt(d2)) <= dist  <=>  d2 <= T  for every float d2 >= 0
-// (sqrt_le's exact bound (dist + ulp/2)^2, rounded down to the float strictly below it):
-// the per-structure test is then the float32 squared norm and one compare, no sqrt.
-__device__ __forceinline__ float sq_bound(float dist) {
-    if (!(dist >= 0.0f)) return -1.0f;
-    if (isinf(dist)) return INFINITY;
-    const double m = (double)dist + 0.5 * ((double)nextafterf(dist, INFINITY) - (double)dist);
-    const double M = m * m;  // exact (m has <= 25 significant bits)
-    float t = (float)M;
-    if ((double)t >= M) t = nextafterf(t, -INFINITY);
-    return t;
-}
 
 // HAP: the copies are summed on the device -- counts is (nhap, nhap) and every pair
 // (i, j) adds its count to (hap_of[i], hap_of[j]) and (hap_of[j], hap_of[i]) (integer

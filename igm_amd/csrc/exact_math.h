@@ -29,6 +29,19 @@ __device__ __forceinline__ bool sqrt_le(float d2, float dist) {
     return (double)d2 < m * m;  // m has <= 25 significant bits: m*m is exact
 }
 
+// The largest float T with  RN(sqrt(d2)) <= dist  <=>  d2 <= T  for every float d2 >= 0
+// (sqrt_le's exact bound (dist + ulp/2)^2, rounded down to the float strictly below it):
+// the per-structure test is then the float32 squared norm and one compare, no sqrt.
+__device__ __forceinline__ float sq_bound(float dist) {
+    if (!(dist >= 0.0f)) return -1.0f;
+    if (isinf(dist)) return INFINITY;
+    const double m = (double)dist + 0.5 * ((double)nextafterf(dist, INFINITY) - (double)dist);
+    const double M = m * m;  // exact (m has <= 25 significant bits)
+    float t = (float)M;
+    if ((double)t >= M) t = nextafterf(t, -INFINITY);
+    return t;
+}
+
 // float('%.Nf' % x) with scale = 10^N (N <= 15): CPython formats the exact binary
 // value rounded half-to-even to N decimals, and float() returns the double nearest
 // that decimal, i.e. RN(k / 10^N).  x*scale is split exactly into hi + lo.

@@ -20,13 +20,19 @@ bin/igm-report) computed on the GPU from the bead-major population.
                        -- the same numbers inside an imaged nucleus (nucleus_shape exp_map), on
                           the level below the lamina of every structure's map (this project's
                           definitions, include/igm_hip.h: igm_report_map_levels / _map_lamina)
+  neighbour_census / inter_chromosomal_fraction / trans_class_fraction / local_compaction
+                       -- this project's per-locus features (the reference has none): who is
+                          next to every bead in every structure (igm_report_neighbours), the
+                          inter-chromosomal contact fraction, the class composition of the
+                          trans neighbourhood, and the Rg of a window of the fibre
   report_population    -- the numeric files bin/igm-report leaves in its output directory
                           (names and formats of the reference); plots, images and the HTML
                           page stay with the reference
 
     python -m igm_amd.report HSS [-c CONFIG] [-l LABEL] [--semiaxes A B C] [--steps ...] [-o DIR]
                              [--hic HCS] [--hic-sigma S] [--hic-inter-sigma S] [--hic-intra-sigma S]
-                             [--hic-contact-range R]
+                             [--hic-contact-range R] [--neighbour-cutoff D] [--min-sep N]
+                             [--compaction-halfwidth W] [--classes FILE]
 
 Every function takes the population as host arrays -- xyz (nbead, nstruct, 3) float32, the
 .hss layout -- or as a steps.PopulationStore, which then also supplies the index arrays
@@ -44,6 +50,9 @@ from . import _lib
 STEPS = ('rgs', 'shells', 'radials', 'damid', 'distance_map')
 OPTIONAL_STEPS = ('hic',)                    # accepted in `steps`, not run by default
 BODY_STEPS = ('bodies',)                     # optional too: the nuclear bodies of an imaged nucleus
+FEATURE_STEPS = ('neighbours', 'compaction')  # optional: the per-locus features mined from a finished run
+DEFAULT_NEIGHBOUR_CUTOFF = 500.0             # centre-to-centre neighbourhood radius, the models' length unit
+MAX_CLASSES = 8                              # class labels of the neighbour census (igm_report_neighbours)
 DEFAULT_SEMIAXES = (5000.0, 5000.0, 5000.0)  # report_radials / report_shells / report_damid
 DEFAULT_DAMID_CONTACT_RANGE = 0.05           # restraints/DamID/contact_range of the reference's config defaults
 
@@ -414,8 +423,167 @@ def average_distance_map(pop, copy_ptr=None, copy_idx=None, hap_chrom=None, ctx=
     return out
 
 
+# ------------------------------------------------------------------ neighbourhood features
+def chain_numbers(chrom, copy):
+    """(nbead,) int32: the number of every bead's (chromosome, copy) chain in chains(chrom,
+    copy) -- two beads are cis iff they share it, so the homologous copy is trans"""
+    _, _, chain_ptr, chain_idx = chains(chrom, copy)
+    out = np.empty(len(chain_idx), np.int32)
+    out[chain_idx] = np.repeat(np.arange(len(chain_ptr) - 1, dtype=np.int32), np.diff(chain_ptr))
+    return out
+
+
+def neighbour_census(pop, cutoff=DEFAULT_NEIGHBOUR_CUTOFF, chain=None, classes=None, nclass=None, min_sep=1,
+                     radii=None, contact_range=None, want_census=True, ctx=None, device=0):
+    """igm_report_neighbours: who is next to every bead in every structure.
+
+    j is a neighbour of i when their float32 distance is <= cutoff (centre to centre, in the
+    models' length unit) or, with radii (at most 16 distinct values) and contact_range, <=
+    contact_range * (r_i + r_j), the contact map's test.  chain (nbead,): equal values are
+    cis; a PopulationStore supplies chain_numbers(store.chrom, store.copy).  classes
+    (nbead,) labels in [-1, nclass), -1 unlabelled; nclass defaults to max(classes) + 1.
+    Bead i itself and its cis partners with |i - j| < min_sep are ignored.
+
+    Returns {'census': (nbead, nstruct, nclass + 2) int32 or None (want_census=False),
+    'sums': (nbead, nclass + 2) int64, 'icp_sum': (nbead,) float64, 'icp_n': (nbead,) int32}.
+    Column 0 is cis, 1 + k the trans partners of class k, the last one the unlabelled trans
+    partners; icp_sum is the sum of trans / (cis + trans) over the icp_n structures in which
+    the bead has a neighbour at all."""
+    xyz, store = _population(pop)
+    nbead, S = xyz.shape[0], xyz.shape[1]
+    if chain is None:
+        if store is None:
+            raise ValueError('chain is required with host arrays')
+        chain = chain_numbers(store.chrom, store.copy)
+    chain = np.ascontiguousarray(chain, np.int32)
+    if chain.shape != (nbead,):
+        raise ValueError('chain must have one entry per bead')
+    if classes is not None:
+        classes = np.ascontiguousarray(classes, np.int32)
+        if classes.shape != (nbead,):
+            raise ValueError('classes must have one entry per bead')
+        if nclass is None:
+            nclass = max(int(classes.max()) + 1, 0)
+    nclass = int(nclass or 0)
+    if classes is None and nclass:
+        classes = np.full(nbead, -1, np.int32)
+    if radii is not None:
+        radii = np.ascontiguousarray(radii, np.float32)
+        if radii.shape != (nbead,):
+            raise ValueError('radii must have one entry per bead')
+        if contact_range is None:
+            raise ValueError('the radii form needs a contact_range')
+    ncol = nclass + 2
+    c = ctx or _lib.context(device)
+    census = np.empty((nbead, S, ncol), np.int32) if want_census else None
+    sums = np.empty((nbead, ncol), np.int64)
+    icp_sum = np.empty(nbead, np.float64)
+    icp_n = np.empty(nbead, np.int32)
+    rc = c.lib.igm_report_neighbours(c.h, 0, xyz.ctypes.data, nbead, S, chain.ctypes.data, _lib.ptr(classes), nclass,
+                                     int(min_sep), float(cutoff), _lib.ptr(radii),
+                                     0.0 if contact_range is None else float(contact_range), _lib.ptr(census),
+                                     sums.ctypes.data, icp_sum.ctypes.data, icp_n.ctypes.data)
+    c.check(rc, 'igm_report_neighbours')
+    return {'census': census, 'sums': sums, 'icp_sum': icp_sum, 'icp_n': icp_n}
+
+
+def _fold_copies(v, copy_ptr, copy_idx):
+    """average_copies; a locus whose copies are all NaN stays NaN without NumPy's warning"""
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore', RuntimeWarning)
+        return average_copies(v, copy_ptr, copy_idx)
+
+
+def icp_of(icp_sum, icp_n):
+    """icp_sum / icp_n per bead, NaN for a bead that never has a neighbour"""
+    icp_n = np.asarray(icp_n)
+    out = np.full(len(icp_n), np.nan)
+    ok = icp_n > 0
+    out[ok] = np.asarray(icp_sum, np.float64)[ok] / icp_n[ok]
+    return out
+
+
+def inter_chromosomal_fraction(pop, cutoff=DEFAULT_NEIGHBOUR_CUTOFF, chain=None, min_sep=1, radii=None,
+                               contact_range=None, copy_ptr=None, copy_idx=None, ctx=None, device=0):
+    """The inter-chromosomal contact fraction (ICP) of every haploid locus, (nhap,) float64:
+    per bead the mean over the structures in which it has a neighbour of trans / (cis +
+    trans) (neighbour_census), folded over the copies with average_copies.  A bead without
+    any neighbour is NaN, and so is a locus whose copies all are."""
+    xyz, store = _population(pop)
+    copy_ptr, copy_idx = _csr(_pick(copy_ptr, store, 'copy_ptr'), _pick(copy_idx, store, 'copy_idx'), xyz.shape[0],
+                              'copy')
+    res = neighbour_census(xyz if store is None else store, cutoff, chain, None, 0, min_sep, radii, contact_range,
+                           want_census=False, ctx=ctx, device=device)
+    return _fold_copies(icp_of(res['icp_sum'], res['icp_n']), copy_ptr, copy_idx)
+
+
+def trans_class_fraction(census, copy_ptr, copy_idx):
+    """(nhap, nclass) float64 from a census (nbead, nstruct, nclass + 2): for class k the
+    median over the (copy, structure) pairs of a locus of n_k / (the labelled trans
+    partners), skipping the pairs without a labelled trans partner; a locus without such a
+    pair is NaN.  Runs on the host."""
+    census = np.asarray(census)
+    nclass = census.shape[2] - 2
+    nhap = len(copy_ptr) - 1
+    out = np.full((nhap, nclass), np.nan)
+    for h in range(nhap if nclass else 0):
+        lab = census[copy_idx[copy_ptr[h]:copy_ptr[h + 1]], :, 1:1 + nclass].reshape(-1, nclass).astype(np.float64)
+        tot = lab.sum(axis=1)
+        ok = tot > 0
+        if nclass and ok.any():
+            out[h] = np.median(lab[ok] / tot[ok, None], axis=0)
+    return out
+
+
+def compaction_windows(chrom, copy, halfwidth=2):
+    """CSR (ptr (nbead + 1), idx) with one row per bead, in bead order: the beads within
+    halfwidth index positions of it on its own chain (chains(chrom, copy)), clipped at the
+    chain's ends."""
+    halfwidth = int(halfwidth)
+    if halfwidth < 0:
+        raise ValueError('halfwidth must be >= 0')
+    _, _, chain_ptr, chain_idx = chains(chrom, copy)
+    rows = [None] * len(chain_idx)
+    for c in range(len(chain_ptr) - 1):
+        beads = chain_idx[chain_ptr[c]:chain_ptr[c + 1]]
+        for p, b in enumerate(beads):
+            rows[b] = beads[max(0, p - halfwidth):p + halfwidth + 1]
+    ptr = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int32)
+    return ptr, np.concatenate(rows).astype(np.int32)
+
+
+def local_compaction(pop, chrom=None, copy=None, halfwidth=2, ctx=None, device=0):
+    """The local compaction of the fibre, (nbead, nstruct) float64: the radius of gyration
+    (igm_report_rg) of the window of compaction_windows around every bead."""
+    xyz, store = _population(pop)
+    chrom, copy = _pick(chrom, store, 'chrom'), _pick(copy, store, 'copy')
+    if len(chrom) != xyz.shape[0] or len(copy) != xyz.shape[0]:
+        raise ValueError('chrom and copy must have one entry per bead')
+    ptr, idx = compaction_windows(chrom, copy, halfwidth)
+    return chain_rgs(xyz, ptr, idx, ctx=ctx, device=device)
+
+
+def haploid_classes(labels, copy_ptr, copy_idx):
+    """(per-bead labels int32, nclass) from one label per haploid locus (an array or the
+    path of a text file; -1 unlabelled), expanded through the copy index.  ValueError for a
+    wrong length or a label outside [-1, 8)."""
+    if isinstance(labels, (str, os.PathLike)):
+        labels = np.loadtxt(os.fspath(labels), dtype=np.int64, ndmin=1)
+    labels = np.asarray(labels)
+    nhap = len(copy_ptr) - 1
+    if labels.shape != (nhap,):
+        raise ValueError('the class labels must hold one entry per haploid locus (%d), got shape %s'
+                         % (nhap, labels.shape))
+    if len(labels) and (labels.min() < -1 or labels.max() >= MAX_CLASSES):
+        raise ValueError('class labels must lie in [-1, %d)' % MAX_CLASSES)
+    out = np.full(int(copy_ptr[-1]), -1, np.int32)
+    out[copy_idx] = np.repeat(labels.astype(np.int32), np.diff(copy_ptr))
+    return out, int(max(labels.max() + 1, 0)) if len(labels) else 0
+
+
 # ------------------------------------------------------------------ the Hi-C comparison
-HIC_MASKS = ('all', 'restrained', 'non_restrained')
+HIC_MASKS =('all', 'restrained', 'non_restrained')
 
 
 def hic_edges():
@@ -716,13 +884,14 @@ def pearson(x, y):
 
 
 def report_population(hss_path, cfg=None, out_dir=None, steps=STEPS, label='', semiaxes=None, ctx=None, device=0,
-                      hic=None, hic_sigma=None, hic_inter_sigma=None, hic_intra_sigma=None, hic_contact_range=None):
+                      hic=None, hic_sigma=None, hic_inter_sigma=None, hic_intra_sigma=None, hic_contact_range=None,
+                      neighbour_cutoff=DEFAULT_NEIGHBOUR_CUTOFF, min_sep=1, compaction_halfwidth=2, classes=None):
     """Write the numeric files of bin/igm-report for the population at hss_path into
     out_dir (default: QC_<label or file name> beside it) and return {relative name: path}.
 
     cfg: an IGM configuration (dict or JSON file); None looks for config_data in the .hss,
     then for igm-config.json beside it (bin/igm-report:236-262).  steps: any of STEPS, and
-    'hic' and 'bodies' (not run by default).  radials, shells and damid need semiaxes
+    'hic', 'bodies' and the FEATURE_STEPS (not run by default).  radials, shells and damid need semiaxes
     (resolve_semiaxes).  On an exp_map nucleus without explicit ones they run in their map
     forms when the configuration names its maps (named_maps): the same file names hold the
     levels below the lamina, density_histo.txt is divided by the real shell volumes (nan for
@@ -737,10 +906,20 @@ def report_population(hss_path, cfg=None, out_dir=None, steps=STEPS, label='', s
     intra_correlations.txt, inter_correlations.txt and -- this project's addition, the
     reference only draws them -- the raw int64 histograms log_histogram2d.npy and
     linear_histogram2d.npy.  When a sigma is not given its imposed / non_imposed columns
-    are nan (the reference then writes no intra rows and zeros in the inter row)."""
+    are nan (the reference then writes no intra rows and zeros in the inter row).
+
+    FEATURE_STEPS (this project's, not run by default either): neighbours writes
+    neighbours/icp.txt (inter_chromosomal_fraction at neighbour_cutoff and min_sep, one value
+    per haploid locus), neighbours/mean_counts.txt (nhap x ncol: the census sums divided by
+    nstruct, averaged over the copies) and, with classes -- one label per haploid locus, an
+    array or a text file, -1 unlabelled, at most 8 classes; a wrong length or a label out of
+    range raises ValueError before anything is written -- neighbours/trans_fraction.txt
+    (trans_class_fraction, nhap x nclass).  compaction writes compaction/local_rg.txt (nhap x
+    2: the mean and the standard deviation over copies and structures of local_compaction at
+    compaction_halfwidth)."""
     from .steps import PopulationStore
     steps = tuple(steps.split(',')) if isinstance(steps, str) else tuple(steps)
-    known = STEPS + OPTIONAL_STEPS + BODY_STEPS
+    known = STEPS + OPTIONAL_STEPS + BODY_STEPS + FEATURE_STEPS
     unknown = [s for s in steps if s not in known]
     if unknown:
         raise ValueError('unknown report steps %s (known: %s)' % (unknown, ', '.join(known)))
@@ -790,6 +969,14 @@ def report_population(hss_path, cfg=None, out_dir=None, steps=STEPS, label='', s
         bodies = (sec['volumes'], sec['struct_map'])
         for v in bodies[0]:
             map_depth_scale(v)
+    bead_classes, nclass = None, 0
+    if 'neighbours' in steps:
+        if not (np.isfinite(neighbour_cutoff) and neighbour_cutoff >= 0) or int(min_sep) < 1:
+            raise ValueError('the neighbours step needs a finite cutoff >= 0 and min_sep >= 1')
+        if classes is not None:
+            bead_classes, nclass = haploid_classes(classes, store.copy_ptr, store.copy_idx)
+    if 'compaction' in steps and int(compaction_halfwidth) < 0:
+        raise ValueError('the compaction step needs a halfwidth >= 0')
     if out_dir is None:
         base = os.path.splitext(os.path.basename(hss_path))[0]
         out_dir = os.path.join(os.path.dirname(hss_path), 'QC_' + (label or base))
@@ -856,6 +1043,23 @@ def report_population(hss_path, cfg=None, out_dir=None, steps=STEPS, label='', s
     if 'distance_map' in steps:
         np.save(path('distance_map/average%s.npy' % tag),
                 average_distance_map(xyz, store.copy_ptr, store.copy_idx, store.hap_chrom, **kw))
+    if 'neighbours' in steps:
+        res = neighbour_census(xyz, neighbour_cutoff, chain_numbers(store.chrom, store.copy), bead_classes, nclass,
+                               int(min_sep), want_census=nclass > 0, **kw)
+        np.savetxt(path('neighbours/icp%s.txt' % tag),
+                   _fold_copies(icp_of(res['icp_sum'], res['icp_n']), store.copy_ptr, store.copy_idx))
+        mean = res['sums'].astype(np.float64) / xyz.shape[1]
+        np.savetxt(path('neighbours/mean_counts%s.txt' % tag),
+                   np.stack([average_copies(mean[:, k], store.copy_ptr, store.copy_idx)
+                             for k in range(mean.shape[1])], axis=1))
+        if nclass:
+            np.savetxt(path('neighbours/trans_fraction%s.txt' % tag),
+                       trans_class_fraction(res['census'], store.copy_ptr, store.copy_idx))
+    if 'compaction' in steps:
+        lrg = local_compaction(xyz, store.chrom, store.copy, int(compaction_halfwidth), **kw)
+        rows = [lrg[store.copy_idx[store.copy_ptr[h]:store.copy_ptr[h + 1]]].ravel()
+                for h in range(len(store.copy_ptr) - 1)]
+        np.savetxt(path('compaction/local_rg%s.txt' % tag), np.array([(r.mean(), r.std()) for r in rows]))
     if 'hic' in steps:
         from . import hss
         hcfg = params['hic']
@@ -894,13 +1098,21 @@ def main(argv=None):
     ap.add_argument('--hic-inter-sigma', type=float, help='Inter-chromosomal probability cutoff for HiC')
     ap.add_argument('--hic-intra-sigma', type=float, help='Intra-chromosomal probability cutoff for HiC')
     ap.add_argument('--hic-contact-range', type=float, help='Probability cutoff for HiC')
+    ap.add_argument('--neighbour-cutoff', type=float, default=DEFAULT_NEIGHBOUR_CUTOFF,
+                    help='Neighbourhood radius of the neighbours step (default: %(default)s)')
+    ap.add_argument('--min-sep', type=int, default=1,
+                    help='Ignore cis neighbours closer than this on the bead index (default: %(default)s)')
+    ap.add_argument('--compaction-halfwidth', type=int, default=2,
+                    help='Beads on either side in the window of the compaction step (default: %(default)s)')
+    ap.add_argument('--classes', help='Text file with one integer class label per haploid locus (-1: unlabelled)')
     a = ap.parse_args(argv)
     if not os.path.isfile(a.hss):
         ap.error('Cannot find file %s' % a.hss)
     written = report_population(a.hss, cfg=a.config, out_dir=a.out_dir, steps=a.steps, label=a.label,
                                 semiaxes=a.semiaxes, hic=a.hic, hic_sigma=a.hic_sigma,
                                 hic_inter_sigma=a.hic_inter_sigma, hic_intra_sigma=a.hic_intra_sigma,
-                                hic_contact_range=a.hic_contact_range)
+                                hic_contact_range=a.hic_contact_range, neighbour_cutoff=a.neighbour_cutoff,
+                                min_sep=a.min_sep, compaction_halfwidth=a.compaction_halfwidth, classes=a.classes)
     for rel in sorted(written):
         print(written[rel])
     return 0

@@ -748,6 +748,55 @@ int igm_report_hic(igm_ctx* ctx, uint32_t flags,
                    int64_t* dense_sums, int64_t* sparse_ints, double* sparse_sumx, double* means,
                    double* centred);
 
+/* Per-bead neighbourhood census: for every (bead, structure) who is next to it -- the
+ * numbers behind the inter-chromosomal contact fraction (ICP) and the composition of the
+ * trans neighbourhood by class label.  The definitions are this project's: the reference
+ * has none.  xyz (nbead, nstruct, 3) f32 as everywhere in the report.
+ *
+ * Per-bead inputs, host pointers in every mode:
+ *   chain (nbead) int32: any values; two beads are cis iff their values are equal.
+ *   cls   (nbead) int32 in [-1, nclass): -1 means unlabelled; may be NULL when nclass == 0.
+ *         0 <= nclass <= 8.
+ *   radii (nbead) f32 or NULL, see below.
+ *
+ * Neighbour test, igm_contact_map's to the bit: d2 = (dx*dx + dy*dy) + dz*dz in float32
+ * with no contraction; j is a neighbour of i iff fl32(sqrt(d2)) <= bound_ij, decided on
+ * the squared norm.
+ *   radii == NULL: bound_ij = cutoff (float32, finite, >= 0), the centre-to-centre form.
+ *   radii given:   bound_ij = fl32(fl32(contact_range) * fl32(r_i + r_j)), exactly
+ *                  igm_contact_map's bound; cutoff is then ignored.  At most 16 distinct
+ *                  radius values (a table of the squared bounds replaces a per-pair float64
+ *                  evaluation): more return IGM_E_UNSUPPORTED.
+ * A comparison with NaN is false: a bead with a non-finite coordinate has no neighbours
+ * and is nobody's neighbour.  d == 0 with cutoff == 0 is a neighbour.
+ *
+ * Exclusions: bead i itself is never counted; a cis partner j with |i - j| < min_sep on
+ * the bead index is ignored (min_sep >= 1; 1 ignores nothing but i); trans partners are
+ * never ignored.
+ *
+ * Outputs, ncol = nclass + 2: column 0 is cis, column 1 + k holds the trans partners of
+ * class k, column nclass + 1 the unlabelled trans partners.  Each may be NULL, not all.
+ *   census  (nbead, nstruct, ncol) int32: the counts of every (bead, structure); follows
+ *           `flags` (IGM_DEVICE_PTRS) like xyz
+ *   sums    (nbead, ncol) int64: census summed over the structures (host pointer)
+ *   icp_sum (nbead) f64: the sum, over exactly the structures counted in icp_n and in
+ *           structure order, of trans / (cis + trans) -- one float64 division of exact
+ *           integers, trans all trans columns together (host pointer).  A rerun is bitwise
+ *           equal.
+ *   icp_n   (nbead) int32: the number of structures with cis + trans > 0 (host pointer)
+ *
+ * nbead <= 65535 (IGM_E_UNSUPPORTED).  IGM_E_INVALID: a NULL xyz or chain, nbead or
+ * nstruct < 1, nclass outside [0, 8], a cls entry outside [-1, nclass), min_sep < 1, a
+ * cutoff (radii NULL) or contact range (radii given) that is negative or not finite, all
+ * four outputs NULL.  After any refusal the context stays usable and no output is written.
+ * Without a census to return, a scratch plane of its size is taken from the context.
+ * Timing: igm_last_kernel_ms "report_neighbours". */
+int igm_report_neighbours(igm_ctx* ctx, uint32_t flags,
+                          const float* xyz, int32_t nbead, int32_t nstruct,
+                          const int32_t* chain, const int32_t* cls, int32_t nclass, int32_t min_sep,
+                          float cutoff, const float* radii, double contact_range,
+                          int32_t* census, int64_t* sums, double* icp_sum, int32_t* icp_n);
+
 #ifdef __cplusplus
 }
 #endif
