@@ -157,6 +157,10 @@ SIGNATURES = {
                               _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     'igm_report_neighbours': (_i32, [_vp, _u32, _vp, _i32, _i32, _vp, _vp, _i32, _i32, ctypes.c_float, _vp, _f64,
                                      _vp, _vp, _vp, _vp]),
+    'igm_report_seed_bodies': (_i32, [_vp, _u32, _vp, _i32, _i32, _vp, _i32, ctypes.c_float, _i32, _i32,
+                                      _vp, _vp, _vp, _vp]),
+    'igm_report_body_features': (_i32, [_vp, _u32, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _f64,
+                                        _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -25,6 +25,12 @@ bin/igm-report) computed on the GPU from the bead-major population.
                           next to every bead in every structure (igm_report_neighbours), the
                           inter-chromosomal contact fraction, the class composition of the
                           trans neighbourhood, and the Rg of a window of the fibre
+  seed_bodies / body_features / body_profiles
+                       -- nuclear bodies that the models do not contain as objects, from seed
+                          loci (this project's definitions too): the places where the seeds
+                          gather in every structure (igm_report_seed_bodies), every bead's
+                          distance to the nearest one, its association frequency and the
+                          TSA-seq signal the population predicts (igm_report_body_features)
   report_population    -- the numeric files bin/igm-report leaves in its output directory
                           (names and formats of the reference); plots, images and the HTML
                           page stay with the reference
@@ -33,6 +39,8 @@ bin/igm-report) computed on the GPU from the bead-major population.
                              [--hic HCS] [--hic-sigma S] [--hic-inter-sigma S] [--hic-intra-sigma S]
                              [--hic-contact-range R] [--neighbour-cutoff D] [--min-sep N]
                              [--compaction-halfwidth W] [--classes FILE]
+                             [--seeds FILE] [--link-cutoff D] [--min-body-size N] [--assoc-cutoff D]
+                             [--tsa-decay K]
 
 Every function takes the population as host arrays -- xyz (nbead, nstruct, 3) float32, the
 .hss layout -- or as a steps.PopulationStore, which then also supplies the index arrays
@@ -51,7 +59,12 @@ STEPS = ('rgs', 'shells', 'radials', 'damid', 'distance_map')
 OPTIONAL_STEPS = ('hic',)                    # accepted in `steps`, not run by default
 BODY_STEPS = ('bodies',)                     # optional too: the nuclear bodies of an imaged nucleus
 FEATURE_STEPS = ('neighbours', 'compaction')  # optional: the per-locus features mined from a finished run
+SEED_STEPS = ('seeded_bodies',)               # optional: nuclear bodies from seed loci (needs --seeds)
 DEFAULT_NEIGHBOUR_CUTOFF = 500.0             # centre-to-centre neighbourhood radius, the models' length unit
+DEFAULT_LINK_CUTOFF = 500.0                  # seeds this close are linked into one body (this project's choice)
+DEFAULT_MIN_BODY_SIZE = 3                    # seeds a component needs to count as a body
+DEFAULT_ASSOC_CUTOFF = 500.0                 # a bead this close to a body's centre is associated with it
+DEFAULT_TSA_DECAY = 0.004                    # per length unit: the TSA-seq signal falls off as exp(-decay * d)
 MAX_CLASSES = 8                              # class labels of the neighbour census (igm_report_neighbours)
 DEFAULT_SEMIAXES = (5000.0, 5000.0, 5000.0)  # report_radials / report_shells / report_damid
 DEFAULT_DAMID_CONTACT_RANGE = 0.05           # restraints/DamID/contact_range of the reference's config defaults
@@ -582,6 +595,110 @@ def haploid_classes(labels, copy_ptr, copy_idx):
     return out, int(max(labels.max() + 1, 0)) if len(labels) else 0
 
 
+# ------------------------------------------------------------------ nuclear bodies from seed loci
+def seed_beads(seeds, copy_ptr, copy_idx):
+    """(nseed,) int32: the ascending bead indices of all copies of the seed loci, from one
+    0/1 flag per haploid locus (an array or the path of a text file).  ValueError for a
+    wrong length, a value outside {0, 1} or no seed at all."""
+    if isinstance(seeds, (str, os.PathLike)):
+        seeds = np.loadtxt(os.fspath(seeds), dtype=np.int64, ndmin=1)
+    seeds = np.asarray(seeds)
+    nhap = len(copy_ptr) - 1
+    if seeds.shape != (nhap,):
+        raise ValueError('the seeds must hold one 0/1 flag per haploid locus (%d), got shape %s'
+                         % (nhap, seeds.shape))
+    if np.any((seeds != 0) & (seeds != 1)):
+        raise ValueError('the seed flags must be 0 or 1')
+    if not np.any(seeds == 1):
+        raise ValueError('no locus is flagged as a seed')
+    flag = np.repeat(seeds == 1, np.diff(copy_ptr))
+    return np.sort(np.asarray(copy_idx)[flag]).astype(np.int32)
+
+
+def seed_bodies(pop, seeds, link_cutoff=DEFAULT_LINK_CUTOFF, min_size=DEFAULT_MIN_BODY_SIZE, want_labels=True,
+                ctx=None, device=0):
+    """igm_report_seed_bodies: the bodies of every structure, the connected components (at
+    least min_size seeds) of the graph that links two seeds whose float32 distance is <=
+    link_cutoff.  seeds: the ascending bead indices (seed_beads), at most 8192.
+
+    Returns {'label': (nstruct, nseed) int32 -- the smallest rank in every seed's component
+    -- or None (want_labels=False), 'nbody': (nstruct,) int32, 'size': (nstruct, K) int32,
+    0 past nbody, 'centre': (nstruct, K, 3) float64, NaN past nbody}, K = nbody.max(); the
+    bodies of a structure are numbered in ascending label."""
+    xyz, _ = _population(pop)
+    nbead, S = xyz.shape[0], xyz.shape[1]
+    seeds = np.ascontiguousarray(seeds, np.int32)
+    if seeds.ndim != 1 or len(seeds) < 1:
+        raise ValueError('seeds must be a non-empty list of bead indices')
+    if int(min_size) < 1:
+        raise ValueError('min_size must be >= 1')
+    nseed = len(seeds)
+    maxb = max(nseed // int(min_size), 1)  # cannot overflow
+    c = ctx or _lib.context(device)
+    label = np.empty((S, nseed), np.int32) if want_labels else None
+    nbody = np.empty(S, np.int32)
+    size = np.empty((S, maxb), np.int32)
+    centre = np.empty((S, maxb, 3), np.float64)
+    rc = c.lib.igm_report_seed_bodies(c.h, 0, xyz.ctypes.data, nbead, S, seeds.ctypes.data, nseed, float(link_cutoff),
+                                      int(min_size), maxb, _lib.ptr(label), nbody.ctypes.data, size.ctypes.data,
+                                      centre.ctypes.data)
+    c.check(rc, 'igm_report_seed_bodies')
+    K = int(nbody.max())
+    return {'label': label, 'nbody': nbody, 'size': np.ascontiguousarray(size[:, :K]),
+            'centre': np.ascontiguousarray(centre[:, :K])}
+
+
+def body_features(pop, nbody, centre, assoc_cutoff=DEFAULT_ASSOC_CUTOFF, decay=DEFAULT_TSA_DECAY, want_nearest=False,
+                  ctx=None, device=0):
+    """igm_report_body_features: every bead against the bodies of every structure.  nbody
+    (nstruct,), centre (nstruct, K, 3) float64 (seed_bodies, or any other source).
+
+    Returns {'nearest': (nbead, nstruct) float64, the distance to the nearest body (NaN in a
+    structure without one), or None (want_nearest=False), 'dist_sum' / 'dist_sqsum':
+    (nbead,) float64 sums of nearest and its square over the structures with a body,
+    'assoc': (nbead,) int64 structures with nearest <= assoc_cutoff, 'tsa_sum': (nbead,)
+    float64, the sum over structures and bodies of exp(-decay * distance)}."""
+    xyz, _ = _population(pop)
+    nbead, S = xyz.shape[0], xyz.shape[1]
+    nbody = np.ascontiguousarray(nbody, np.int32)
+    centre = np.ascontiguousarray(centre, np.float64)
+    if nbody.shape != (S,) or centre.ndim != 3 or centre.shape[0] != S or centre.shape[2] != 3:
+        raise ValueError('nbody must be (nstruct,) and centre (nstruct, K, 3)')
+    if centre.shape[1] == 0:  # no structure has a body: one unread slot per structure
+        centre = np.full((S, 1, 3), np.nan)
+    c = ctx or _lib.context(device)
+    nearest = np.empty((nbead, S), np.float64) if want_nearest else None
+    out = {'nearest': nearest, 'dist_sum': np.empty(nbead, np.float64), 'dist_sqsum': np.empty(nbead, np.float64),
+           'assoc': np.empty(nbead, np.int64), 'tsa_sum': np.empty(nbead, np.float64)}
+    rc = c.lib.igm_report_body_features(c.h, 0, xyz.ctypes.data, nbead, S, nbody.ctypes.data, centre.ctypes.data,
+                                        centre.shape[1], float(assoc_cutoff), float(decay), _lib.ptr(nearest),
+                                        out['dist_sum'].ctypes.data, out['dist_sqsum'].ctypes.data,
+                                        out['assoc'].ctypes.data, out['tsa_sum'].ctypes.data)
+    c.check(rc, 'igm_report_body_features')
+    return out
+
+
+def body_profiles(features, nbody, copy_ptr, copy_idx):
+    """(nhap, 4) float64 per haploid locus from body_features: the mean distance to the
+    nearest body, its standard deviation, the association frequency and the TSA signal.
+    Per bead, over the n structures that have a body: mean = dist_sum / n, std =
+    sqrt(max(0, dist_sqsum / n - mean^2)), frequency = assoc / n; TSA = tsa_sum / nstruct;
+    then folded over the copies (_fold_copies).  n == 0 gives NaN, except TSA, which is 0."""
+    nbody = np.asarray(nbody)
+    S, n = len(nbody), int(np.count_nonzero(nbody > 0))
+    dsum = np.asarray(features['dist_sum'], np.float64)
+    cols = np.full((len(dsum), 4), np.nan)
+    cols[:, 3] = np.asarray(features['tsa_sum'], np.float64) / S
+    if n:
+        with np.errstate(invalid='ignore', over='ignore'):
+            mean = dsum / n
+            var = np.asarray(features['dist_sqsum'], np.float64) / n - mean * mean
+            cols[:, 0] = mean
+            cols[:, 1] = np.sqrt(np.where(var < 0, 0.0, var))  # a NaN stays one
+            cols[:, 2] = np.asarray(features['assoc'], np.float64) / n
+    return np.stack([_fold_copies(cols[:, k], copy_ptr, copy_idx) for k in range(4)], axis=1)
+
+
 # ------------------------------------------------------------------ the Hi-C comparison
 HIC_MASKS =('all', 'restrained', 'non_restrained')
 
@@ -885,7 +1002,9 @@ def pearson(x, y):
 
 def report_population(hss_path, cfg=None, out_dir=None, steps=STEPS, label='', semiaxes=None, ctx=None, device=0,
                       hic=None, hic_sigma=None, hic_inter_sigma=None, hic_intra_sigma=None, hic_contact_range=None,
-                      neighbour_cutoff=DEFAULT_NEIGHBOUR_CUTOFF, min_sep=1, compaction_halfwidth=2, classes=None):
+                      neighbour_cutoff=DEFAULT_NEIGHBOUR_CUTOFF, min_sep=1, compaction_halfwidth=2, classes=None,
+                      seeds=None, link_cutoff=DEFAULT_LINK_CUTOFF, min_body_size=DEFAULT_MIN_BODY_SIZE,
+                      assoc_cutoff=DEFAULT_ASSOC_CUTOFF, tsa_decay=DEFAULT_TSA_DECAY):
     """Write the numeric files of bin/igm-report for the population at hss_path into
     out_dir (default: QC_<label or file name> beside it) and return {relative name: path}.
 
@@ -916,10 +1035,18 @@ def report_population(hss_path, cfg=None, out_dir=None, steps=STEPS, label='', s
     range raises ValueError before anything is written -- neighbours/trans_fraction.txt
     (trans_class_fraction, nhap x nclass).  compaction writes compaction/local_rg.txt (nhap x
     2: the mean and the standard deviation over copies and structures of local_compaction at
-    compaction_halfwidth)."""
+    compaction_halfwidth).
+
+    seeded_bodies (not run by default) needs seeds -- one 0/1 flag per haploid locus, an
+    array or a text file (seed_beads); without them it raises a ValueError that names
+    --seeds, and a bad cutoff, decay or size raises before anything is written.  It writes
+    seeded_bodies/count.txt (the bodies of every structure, seed_bodies at link_cutoff and
+    min_body_size), seeded_bodies/centres.txt (rows of structure, body, size, x, y, z) and
+    seeded_bodies/profiles.txt (nhap x 4: body_profiles of body_features at assoc_cutoff and
+    tsa_decay)."""
     from .steps import PopulationStore
     steps = tuple(steps.split(',')) if isinstance(steps, str) else tuple(steps)
-    known = STEPS + OPTIONAL_STEPS + BODY_STEPS + FEATURE_STEPS
+    known = STEPS + OPTIONAL_STEPS + BODY_STEPS + FEATURE_STEPS + SEED_STEPS
     unknown = [s for s in steps if s not in known]
     if unknown:
         raise ValueError('unknown report steps %s (known: %s)' % (unknown, ', '.join(known)))
@@ -977,6 +1104,17 @@ def report_population(hss_path, cfg=None, out_dir=None, steps=STEPS, label='', s
             bead_classes, nclass = haploid_classes(classes, store.copy_ptr, store.copy_idx)
     if 'compaction' in steps and int(compaction_halfwidth) < 0:
         raise ValueError('the compaction step needs a halfwidth >= 0')
+    seed_idx = None
+    if 'seeded_bodies' in steps:
+        if seeds is None:
+            raise ValueError('the seeded_bodies step needs the seed loci: --seeds FILE, one 0/1 flag per haploid '
+                             'locus')
+        for name, v in (('link cutoff', link_cutoff), ('association cutoff', assoc_cutoff), ('TSA decay', tsa_decay)):
+            if not (np.isfinite(v) and v >= 0):
+                raise ValueError('the seeded_bodies step needs a finite %s >= 0' % name)
+        if int(min_body_size) < 1:
+            raise ValueError('the seeded_bodies step needs a minimum body size >= 1')
+        seed_idx = seed_beads(seeds, store.copy_ptr, store.copy_idx)
     if out_dir is None:
         base = os.path.splitext(os.path.basename(hss_path))[0]
         out_dir = os.path.join(os.path.dirname(hss_path), 'QC_' + (label or base))
@@ -1060,6 +1198,17 @@ def report_population(hss_path, cfg=None, out_dir=None, steps=STEPS, label='', s
         rows = [lrg[store.copy_idx[store.copy_ptr[h]:store.copy_ptr[h + 1]]].ravel()
                 for h in range(len(store.copy_ptr) - 1)]
         np.savetxt(path('compaction/local_rg%s.txt' % tag), np.array([(r.mean(), r.std()) for r in rows]))
+    if 'seeded_bodies' in steps:
+        found = seed_bodies(xyz, seed_idx, link_cutoff, int(min_body_size), want_labels=False, **kw)
+        nbody, size, centre = found['nbody'], found['size'], found['centre']
+        np.savetxt(path('seeded_bodies/count%s.txt' % tag), nbody, fmt='%d')
+        with open(path('seeded_bodies/centres%s.txt' % tag), 'w') as f:
+            for s in range(len(nbody)):
+                for k in range(nbody[s]):
+                    f.write('%d %d %d %.17g %.17g %.17g\n' % ((s, k, size[s, k]) + tuple(centre[s, k])))
+        feat = body_features(xyz, nbody, centre, assoc_cutoff, tsa_decay, **kw)
+        np.savetxt(path('seeded_bodies/profiles%s.txt' % tag),
+                   body_profiles(feat, nbody, store.copy_ptr, store.copy_idx))
     if 'hic' in steps:
         from . import hss
         hcfg = params['hic']
@@ -1105,6 +1254,16 @@ def main(argv=None):
     ap.add_argument('--compaction-halfwidth', type=int, default=2,
                     help='Beads on either side in the window of the compaction step (default: %(default)s)')
     ap.add_argument('--classes', help='Text file with one integer class label per haploid locus (-1: unlabelled)')
+    ap.add_argument('--seeds', help='Text file with one 0/1 flag per haploid locus: the seed loci of the '
+                                    'seeded_bodies step')
+    ap.add_argument('--link-cutoff', type=float, default=DEFAULT_LINK_CUTOFF,
+                    help='Seeds this close are linked into one body (default: %(default)s)')
+    ap.add_argument('--min-body-size', type=int, default=DEFAULT_MIN_BODY_SIZE,
+                    help='Seeds a component needs to count as a body (default: %(default)s)')
+    ap.add_argument('--assoc-cutoff', type=float, default=DEFAULT_ASSOC_CUTOFF,
+                    help='A bead this close to a body centre is associated with it (default: %(default)s)')
+    ap.add_argument('--tsa-decay', type=float, default=DEFAULT_TSA_DECAY,
+                    help='Decay of the predicted TSA-seq signal per length unit (default: %(default)s)')
     a = ap.parse_args(argv)
     if not os.path.isfile(a.hss):
         ap.error('Cannot find file %s' % a.hss)
@@ -1112,7 +1271,9 @@ def main(argv=None):
                                 semiaxes=a.semiaxes, hic=a.hic, hic_sigma=a.hic_sigma,
                                 hic_inter_sigma=a.hic_inter_sigma, hic_intra_sigma=a.hic_intra_sigma,
                                 hic_contact_range=a.hic_contact_range, neighbour_cutoff=a.neighbour_cutoff,
-                                min_sep=a.min_sep, compaction_halfwidth=a.compaction_halfwidth, classes=a.classes)
+                                min_sep=a.min_sep, compaction_halfwidth=a.compaction_halfwidth, classes=a.classes,
+                                seeds=a.seeds, link_cutoff=a.link_cutoff, min_body_size=a.min_body_size,
+                                assoc_cutoff=a.assoc_cutoff, tsa_decay=a.tsa_decay)
     for rel in sorted(written):
         print(written[rel])
     return 0

@@ -797,6 +797,89 @@ int igm_report_neighbours(igm_ctx* ctx, uint32_t flags,
                           float cutoff, const float* radii, double contact_range,
                           int32_t* census, int64_t* sums, double* icp_sum, int32_t* icp_n);
 
+/* Nuclear bodies from seed loci: features measured against bodies that the models do not
+ * contain as objects (speckles; nucleoli on a run without body maps).  The loci known to
+ * sit at the body are the seeds; in every structure the places where seeds gather are its
+ * bodies; every bead then gets its distance to the nearest body, how often it lies within
+ * reach of one, and the TSA-seq signal the population predicts.  The definitions are this
+ * project's: the reference has none.  The models' length unit applies throughout (nm in
+ * IGM's files); xyz (nbead, nstruct, 3) f32 as everywhere in the report.  Two calls: the
+ * first finds the bodies, the second measures against any set of centres.
+ *
+ * The published recipe clusters the seeds with Markov clustering.  That has no
+ * order-independent answer (its result depends on inflation, pruning and iteration order),
+ * so single linkage at a fixed cutoff stands in for it here: the answer below is unique
+ * whatever order the work is done in.
+ *
+ * Seeds and links.  seed_idx (nseed) int32: bead indices, strictly increasing, in [0, nbead);
+ * the rank of a seed is its position in that list.  Two seeds p != q of a structure are
+ * linked iff igm_report_neighbours' test in its centre-to-centre form holds for
+ * link_cutoff: d2 = (dx*dx + dy*dy) + dz*dz in float32 with no contraction, linked iff
+ * fl32(sqrt(d2)) <= link_cutoff, decided on the squared norm.  A comparison with NaN is
+ * false: a seed with a non-finite coordinate is linked to nobody.  link_cutoff == 0 links
+ * coincident seeds.
+ *
+ * Bodies.  The components of a structure are the connected components of its link graph;
+ * the label of a seed is the smallest rank in its component.  A body is a component with
+ * at least min_size seeds (min_size >= 1); the bodies of a structure are numbered in
+ * ascending label.  The centre of a body is the sum of its members' coordinates, each
+ * widened to float64 and added in ascending rank, divided once by the member count
+ * (float64).  A body with a non-finite member has a non-finite centre.
+ *
+ * Outputs of igm_report_seed_bodies, host pointers in every mode (of the inputs only xyz
+ * follows `flags`):
+ *   label  (nstruct, nseed) int32: every seed's label; may be NULL
+ *   nbody  (nstruct) int32: the number of bodies, the true count also on overflow
+ *   size   (nstruct, max_bodies) int32: the member counts, 0 past nbody; may be NULL
+ *   centre (nstruct, max_bodies, 3) f64: NaN past nbody; may be NULL
+ * IGM_E_INVALID: a NULL xyz, seed_idx or nbody; nbead, nstruct or nseed < 1; seeds not
+ * strictly increasing or out of range; a link_cutoff that is negative or not finite;
+ * min_size < 1; max_bodies < 0, or < 1 while size or centre is given.
+ * IGM_E_UNSUPPORTED: nseed > 8192 (the seeds of one structure live in LDS, 16 B each).
+ * IGM_E_OVERFLOW: some structure has more than max_bodies bodies; nbody then holds the
+ * true counts and nothing else is written.  After any other refusal no output is written;
+ * the context stays usable after every refusal.  max_bodies = nseed / min_size cannot
+ * overflow.  Timing: igm_last_kernel_ms "report_seed_bodies". */
+int igm_report_seed_bodies(igm_ctx* ctx, uint32_t flags,
+                           const float* xyz, int32_t nbead, int32_t nstruct,
+                           const int32_t* seed_idx, int32_t nseed, float link_cutoff, int32_t min_size,
+                           int32_t max_bodies,
+                           int32_t* label, int32_t* nbody, int32_t* size, double* centre);
+
+/* The per-bead features against the bodies of every structure.  nbody (nstruct) int32 in
+ * [0, max_bodies] and centre (nstruct, max_bodies, 3) f64 are host pointers and may come
+ * from anywhere -- igm_report_seed_bodies, an imaging experiment; only the first nbody[s]
+ * centres of structure s are read, and they must be finite.
+ *
+ * For bead p and body k of structure s: t = f64(p) - c_k and
+ * d = sqrt((t0*t0 + t1*t1) + t2*t2), correctly rounded float64 with no contraction; where
+ * a coordinate of p in s is not finite, d is NaN for every body.  nearest(p, s) is the
+ * minimum of d over the bodies of s in body order (the first on ties), NaN when s has no
+ * body.  t(p, s) is the sum over the bodies, in body order from 0, of exp(-(decay * d)),
+ * the argument one float64 multiply; a structure without bodies has t = 0.
+ *
+ * Outputs; each may be NULL, not all.  The float64 sums run over the structures in
+ * structure order (as level_mean of igm_report_levels), so a rerun is bitwise equal.
+ *   nearest    (nbead, nstruct) f64; follows `flags` (IGM_DEVICE_PTRS) like xyz
+ *   dist_sum   (nbead) f64: the sum of nearest over the structures that have a body
+ *   dist_sqsum (nbead) f64: the sum of fl64(nearest * nearest) over the same structures
+ *   assoc      (nbead) int64: the number of structures with nearest <= assoc_cutoff
+ *   tsa_sum    (nbead) f64: the sum of t(p, s) over all structures
+ * The per-bead outputs are host pointers in every mode.  A bead with a non-finite
+ * coordinate in a structure that has a body has NaN in its float sums and is not
+ * associated there.
+ * IGM_E_INVALID: a NULL xyz, nbody or centre; nbead, nstruct or max_bodies < 1; an nbody
+ * entry outside [0, max_bodies]; a non-finite centre among the first nbody[s] of a
+ * structure; assoc_cutoff or decay negative or not finite; every output NULL.  After a
+ * refusal the context stays usable and no output is written.
+ * Timing: igm_last_kernel_ms "report_body_features". */
+int igm_report_body_features(igm_ctx* ctx, uint32_t flags,
+                             const float* xyz, int32_t nbead, int32_t nstruct,
+                             const int32_t* nbody, const double* centre, int32_t max_bodies,
+                             double assoc_cutoff, double decay,
+                             double* nearest, double* dist_sum, double* dist_sqsum, int64_t* assoc,
+                             double* tsa_sum);
+
 #ifdef __cplusplus
 }
 #endif
