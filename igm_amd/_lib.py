@@ -161,6 +161,8 @@ SIGNATURES = {
                                       _vp, _vp, _vp, _vp]),
     'igm_report_body_features': (_i32, [_vp, _u32, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _f64,
                                         _vp, _vp, _vp, _vp, _vp]),
+    'igm_report_conformations': (_i32, [_vp, _u32, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _i32,
+                                        _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -41,6 +41,8 @@ SOURCES = {
     # fp64 sums and a Jacobi eigenvalue: nothing is restated bit for bit, FMAs are welcome
     'tracing_assign.hip': [],
     'tracing_cells.hip': [],
+    # the tracing A-steps' eigen-solve after a tiled fp64 Gram product: FMAs are welcome here too
+    'report_conformations.hip': [],
 }
 # host-only C++ (no device code): the .hss / actdist.hdf5 reader and writer
 HOST_SOURCES = {'h5io.cpp': []}

@@ -31,6 +31,12 @@ bin/igm-report) computed on the GPU from the bead-major population.
                           gather in every structure (igm_report_seed_bodies), every bead's
                           distance to the nearest one, its association frequency and the
                           TSA-seq signal the population predicts (igm_report_body_features)
+  conformation_beads / conformation_rmsd / conformation_summary
+                       -- how different the structures are from each other (this project's
+                          definitions as well): the minimal RMSD after optimal superposition
+                          between every two copies of a chromosome across the population
+                          (igm_report_conformations), its mean, the medoid conformation and
+                          the homologues of one cell against those of different cells
   report_population    -- the numeric files bin/igm-report leaves in its output directory
                           (names and formats of the reference); plots, images and the HTML
                           page stay with the reference
@@ -41,6 +47,8 @@ bin/igm-report) computed on the GPU from the bead-major population.
                              [--compaction-halfwidth W] [--classes FILE]
                              [--seeds FILE] [--link-cutoff D] [--min-body-size N] [--assoc-cutoff D]
                              [--tsa-decay K]
+                             [--conformation-chroms ID[,ID...]] [--conformation-loci FILE] [--save-rmsd]
+                             [--rmsd-max D] [--rmsd-bins N]
 
 Every function takes the population as host arrays -- xyz (nbead, nstruct, 3) float32, the
 .hss layout -- or as a steps.PopulationStore, which then also supplies the index arrays
@@ -60,6 +68,10 @@ OPTIONAL_STEPS = ('hic',)                    # accepted in `steps`, not run by d
 BODY_STEPS = ('bodies',)                     # optional too: the nuclear bodies of an imaged nucleus
 FEATURE_STEPS = ('neighbours', 'compaction')  # optional: the per-locus features mined from a finished run
 SEED_STEPS = ('seeded_bodies',)               # optional: nuclear bodies from seed loci (needs --seeds)
+CONFORMATION_STEPS = ('conformations',)       # optional: pairwise RMSD of the copies of every chromosome
+DEFAULT_RMSD_MAX = 10000.0                   # the RMSD histogram: 200 bins up to this, the models' length unit
+DEFAULT_RMSD_BINS = 200                      # (this project's choice)
+MAX_RMSD_BINS = 4096                         # igm_report_conformations counts the bins in LDS
 DEFAULT_NEIGHBOUR_CUTOFF = 500.0             # centre-to-centre neighbourhood radius, the models' length unit
 DEFAULT_LINK_CUTOFF = 500.0                  # seeds this close are linked into one body (this project's choice)
 DEFAULT_MIN_BODY_SIZE = 3                    # seeds a component needs to count as a body
@@ -699,6 +711,139 @@ def body_profiles(features, nbody, copy_ptr, copy_idx):
     return np.stack([_fold_copies(cols[:, k], copy_ptr, copy_idx) for k in range(4)], axis=1)
 
 
+# ------------------------------------------------------------------ pairwise conformation RMSD
+def rmsd_edges_of(rmsd_max=DEFAULT_RMSD_MAX, rmsd_bins=DEFAULT_RMSD_BINS):
+    """np.linspace(0, rmsd_max, rmsd_bins + 1) as float32: the edges of the RMSD histogram.
+    ValueError unless rmsd_max is finite and > 0, rmsd_bins an integer in [1, 4096] and the
+    float32 edges come out strictly increasing."""
+    if not (np.isfinite(rmsd_max) and rmsd_max > 0):
+        raise ValueError('the RMSD histogram needs a finite maximum > 0 (--rmsd-max)')
+    if int(rmsd_bins) != rmsd_bins or not 1 <= int(rmsd_bins) <= MAX_RMSD_BINS:
+        raise ValueError('the RMSD histogram needs between 1 and %d bins (--rmsd-bins)' % MAX_RMSD_BINS)
+    return _rmsd_edges(np.linspace(0.0, float(rmsd_max), int(rmsd_bins) + 1))
+
+
+def _rmsd_edges(edges):
+    e = np.ascontiguousarray(edges, np.float32)
+    if e.ndim != 1 or not 2 <= len(e) <= MAX_RMSD_BINS + 1 or not np.all(np.isfinite(e)) or np.any(np.diff(e) <= 0):
+        raise ValueError('the RMSD histogram edges must be 2 to %d finite, strictly increasing float32 values'
+                         % (MAX_RMSD_BINS + 1))
+    return e
+
+
+def conformation_beads(chrom, copy, copy_ptr, copy_idx, chrom_id, loci=None):
+    """(ncopy, nlocus) int32: the beads of the haploid loci of chromosome chrom_id under each
+    of its copies (ascending copy number), in locus order -- the `bead` table of
+    igm_report_conformations.  loci: one 0/1 flag per haploid locus of the genome (an array
+    or the path of a text file, the convention of seed_beads) that restricts the group, to
+    one domain say.  ValueError for a wrong length, a flag other than 0 or 1, a chromosome
+    that is not there or is left without loci, and loci whose copies are not the
+    chromosome's."""
+    chrom, copy = np.asarray(chrom), np.asarray(copy)
+    copy_ptr, copy_idx = np.asarray(copy_ptr), np.asarray(copy_idx)
+    nhap = len(copy_ptr) - 1
+    pick = chrom[copy_idx[copy_ptr[:-1]]] == chrom_id
+    if loci is not None:
+        if isinstance(loci, (str, os.PathLike)):
+            loci = np.loadtxt(os.fspath(loci), dtype=np.int64, ndmin=1)
+        loci = np.asarray(loci)
+        if loci.shape != (nhap,):
+            raise ValueError('the loci must hold one 0/1 flag per haploid locus (%d), got shape %s'
+                             % (nhap, loci.shape))
+        if np.any((loci != 0) & (loci != 1)):
+            raise ValueError('the locus flags must be 0 or 1')
+        pick = pick & (loci == 1)
+    hs = np.flatnonzero(pick)
+    if len(hs) == 0:
+        raise ValueError('chromosome %s has no loci to compare' % (chrom_id,))
+    copies = np.unique(copy[chrom == chrom_id])
+    if np.any(np.diff(copy_ptr)[hs] != len(copies)):
+        raise ValueError('the loci of chromosome %s do not all have its %d copies' % (chrom_id, len(copies)))
+    table = copy_idx[copy_ptr[hs][:, None] + np.arange(len(copies))[None, :]]      # (nlocus, ncopy)
+    table = np.take_along_axis(table, np.argsort(copy[table], axis=1, kind='stable'), axis=1)
+    if np.any(copy[table] != copies[None, :]) or np.any(chrom[table] != chrom_id):
+        raise ValueError('the loci of chromosome %s do not all have its %d copies' % (chrom_id, len(copies)))
+    return np.ascontiguousarray(table.T, np.int32)
+
+
+def conformation_rmsd(pop, beads, edges=None, want_matrix=True, ctx=None, device=0):
+    """igm_report_conformations on one group: beads (ncopy, nlocus) int32 (conformation_beads),
+    conformation a = copy * nstruct + structure, M = ncopy * nstruct of them.
+
+    Returns {'rmsd': (M, M) float32, the minimal RMSD after optimal rigid superposition of
+    every two conformations, or None (want_matrix=False: every other entry has the same
+    bytes without it), 'g': (M,) float64 sum of squared distances to the conformation's
+    centre, 'row_sum' / 'row_n': (M,) float64 / int32, the sum and the number of the finite
+    RMSDs to the other conformations, 'same': (nstruct, ncopy, ncopy) float32, the copies of
+    one structure against each other, 'hist': (len(edges) - 1,) int64 over the pairs a < b
+    (np.histogram on the float32 values) or None without edges, 'edges', 'nlocus'}.  A
+    conformation with a non-finite coordinate has NaN in g, in its row and column, and
+    counts nowhere."""
+    xyz, _ = _population(pop)
+    nbead, S = xyz.shape[0], xyz.shape[1]
+    beads = np.ascontiguousarray(beads, np.int32)
+    if beads.ndim != 2 or beads.shape[0] < 1 or beads.shape[1] < 1:
+        raise ValueError('beads must be (ncopy, nlocus) with ncopy, nlocus >= 1')
+    ncopy, nlocus = beads.shape
+    M = ncopy * S
+    e = _rmsd_edges(edges) if edges is not None else None
+    c = ctx or _lib.context(device)
+    out = {'rmsd': np.empty((M, M), np.float32) if want_matrix else None, 'g': np.empty(M, np.float64),
+           'row_sum': np.empty(M, np.float64), 'row_n': np.empty(M, np.int32),
+           'same': np.empty((S, ncopy, ncopy), np.float32),
+           'hist': np.empty(len(e) - 1, np.int64) if e is not None else None, 'edges': e, 'nlocus': nlocus}
+    rc = c.lib.igm_report_conformations(c.h, 0, xyz.ctypes.data, nbead, S, beads.ctypes.data, ncopy, nlocus,
+                                        _lib.ptr(e), 0 if e is None else len(e), _lib.ptr(out['rmsd']),
+                                        out['g'].ctypes.data, out['row_sum'].ctypes.data, out['row_n'].ctypes.data,
+                                        out['same'].ctypes.data, _lib.ptr(out['hist']))
+    c.check(rc, 'igm_report_conformations')
+    return out
+
+
+def conformation_summary(out, nstruct):
+    """The numbers people take from conformation_rmsd's reductions, on the host and without
+    the matrix: {'mean_rmsd': (M,) row_sum / row_n (NaN where row_n == 0), 'mean': the
+    population mean pairwise RMSD sum(row_sum) / sum(row_n), 'mean_rg': the mean of
+    sqrt(g / nlocus) over the conformations with a finite g, 'variability': mean / mean_rg,
+    'medoid': (structure, copy) of the conformation with the smallest mean_rmsd, the lowest
+    index on ties (the first conformation with a finite g when no mean is defined, (-1, -1)
+    without one), 'medoid_mean_rmsd', and for ncopy > 1 (NaN otherwise) 'same_mean': the mean
+    finite RMSD between copies of the same structure (from `same`), 'different_mean': between
+    copies of different structures -- the total minus the same-structure pairs, as sums --
+    and 'ratio' = same_mean / different_mean}."""
+    g = np.asarray(out['g'], np.float64)
+    row_sum, row_n = np.asarray(out['row_sum'], np.float64), np.asarray(out['row_n'], np.int64)
+    M, S = len(g), int(nstruct)
+    if S < 1 or M % S:
+        raise ValueError('%d conformations are not a whole number of copies of %d structures' % (M, S))
+    ncopy = M // S
+    nan = float('nan')
+    with np.errstate(invalid='ignore', divide='ignore'):
+        mean_rmsd = np.where(row_n > 0, row_sum / row_n, np.nan)
+    tot_sum, tot_n = float(row_sum.sum()), int(row_n.sum())          # every pair twice in both
+    mean = tot_sum / tot_n if tot_n else nan
+    fin = np.isfinite(g)
+    mean_rg = float(np.sqrt(g[fin] / out['nlocus']).mean()) if fin.any() else nan
+    res = {'mean_rmsd': mean_rmsd, 'mean': mean, 'mean_rg': mean_rg,
+           'variability': mean / mean_rg if mean_rg > 0 else nan,
+           'same_mean': nan, 'different_mean': nan, 'ratio': nan}
+    if np.isfinite(mean_rmsd).any():
+        a = int(np.nanargmin(mean_rmsd))
+    else:
+        a = int(np.argmax(fin)) if fin.any() else -1
+    res['medoid'] = (a % S, a // S) if a >= 0 else (-1, -1)
+    res['medoid_mean_rmsd'] = float(mean_rmsd[a]) if a >= 0 else nan
+    if ncopy > 1:
+        same = np.asarray(out['same'], np.float64).reshape(S, ncopy, ncopy)
+        off = np.isfinite(same) & ~np.eye(ncopy, dtype=bool)[None]
+        same_sum, same_n = float(same[off].sum()), int(off.sum())       # every pair twice here too
+        diff_sum, diff_n = tot_sum - same_sum, tot_n - same_n
+        res['same_mean'] = same_sum / same_n if same_n else nan
+        res['different_mean'] = diff_sum / diff_n if diff_n else nan
+        res['ratio'] = res['same_mean'] / res['different_mean'] if res['different_mean'] > 0 else nan
+    return res
+
+
 # ------------------------------------------------------------------ the Hi-C comparison
 HIC_MASKS =('all', 'restrained', 'non_restrained')
 
@@ -1004,13 +1149,15 @@ def report_population(hss_path, cfg=None, out_dir=None, steps=STEPS, label='', s
                       hic=None, hic_sigma=None, hic_inter_sigma=None, hic_intra_sigma=None, hic_contact_range=None,
                       neighbour_cutoff=DEFAULT_NEIGHBOUR_CUTOFF, min_sep=1, compaction_halfwidth=2, classes=None,
                       seeds=None, link_cutoff=DEFAULT_LINK_CUTOFF, min_body_size=DEFAULT_MIN_BODY_SIZE,
-                      assoc_cutoff=DEFAULT_ASSOC_CUTOFF, tsa_decay=DEFAULT_TSA_DECAY):
+                      assoc_cutoff=DEFAULT_ASSOC_CUTOFF, tsa_decay=DEFAULT_TSA_DECAY, conformation_chroms=None,
+                      conformation_loci=None, save_rmsd=False, rmsd_edges=None):
     """Write the numeric files of bin/igm-report for the population at hss_path into
     out_dir (default: QC_<label or file name> beside it) and return {relative name: path}.
 
     cfg: an IGM configuration (dict or JSON file); None looks for config_data in the .hss,
     then for igm-config.json beside it (bin/igm-report:236-262).  steps: any of STEPS, and
-    'hic', 'bodies' and the FEATURE_STEPS (not run by default).  radials, shells and damid need semiaxes
+    'hic', 'bodies', the FEATURE_STEPS, 'seeded_bodies' and 'conformations' (not run by
+    default).  radials, shells and damid need semiaxes
     (resolve_semiaxes).  On an exp_map nucleus without explicit ones they run in their map
     forms when the configuration names its maps (named_maps): the same file names hold the
     levels below the lamina, density_histo.txt is divided by the real shell volumes (nan for
@@ -1043,10 +1190,24 @@ def report_population(hss_path, cfg=None, out_dir=None, steps=STEPS, label='', s
     seeded_bodies/count.txt (the bodies of every structure, seed_bodies at link_cutoff and
     min_body_size), seeded_bodies/centres.txt (rows of structure, body, size, x, y, z) and
     seeded_bodies/profiles.txt (nhap x 4: body_profiles of body_features at assoc_cutoff and
-    tsa_decay)."""
+    tsa_decay).
+
+    conformations (not run by default) compares the copies of every chromosome in
+    conformation_chroms (ids as in the index; None: all of them) across the population by
+    their minimal RMSD after superposition (conformation_rmsd), on the loci flagged in
+    conformation_loci (one 0/1 flag per haploid locus, an array or a text file; None: all).
+    It writes conformations/summary.txt (one row per chromosome: id, nlocus, ncopy, M, mean
+    RMSD, mean Rg, variability, medoid structure, medoid copy, the medoid's mean RMSD, the
+    same-structure mean, the different-structure mean, their ratio -- nan for a single
+    copy; conformation_summary), conformations/<id>_mean_rmsd.txt (M values, conformation
+    copy * nstruct + structure), conformations/histogram.txt (one row per bin of rmsd_edges,
+    default rmsd_edges_of(): its lower and upper edge, then one count column per
+    chromosome) and with save_rmsd conformations/<id>_rmsd.npy, the (M, M) float32 matrix.
+    A chromosome id that is not in the index, bad loci or bad edges raise ValueError before
+    anything is written."""
     from .steps import PopulationStore
     steps = tuple(steps.split(',')) if isinstance(steps, str) else tuple(steps)
-    known = STEPS + OPTIONAL_STEPS + BODY_STEPS + FEATURE_STEPS + SEED_STEPS
+    known = STEPS + OPTIONAL_STEPS + BODY_STEPS + FEATURE_STEPS + SEED_STEPS + CONFORMATION_STEPS
     unknown = [s for s in steps if s not in known]
     if unknown:
         raise ValueError('unknown report steps %s (known: %s)' % (unknown, ', '.join(known)))
@@ -1115,6 +1276,17 @@ def report_population(hss_path, cfg=None, out_dir=None, steps=STEPS, label='', s
         if int(min_body_size) < 1:
             raise ValueError('the seeded_bodies step needs a minimum body size >= 1')
         seed_idx = seed_beads(seeds, store.copy_ptr, store.copy_idx)
+    groups, edges32 = [], None
+    if 'conformations' in steps:
+        edges32 = rmsd_edges_of() if rmsd_edges is None else _rmsd_edges(rmsd_edges)
+        have = np.unique(store.chrom)
+        want = have if conformation_chroms is None else np.atleast_1d(np.asarray(conformation_chroms))
+        for cid in want:
+            if cid not in have:
+                raise ValueError('the conformations step: chromosome id %s is not in the index (ids: %s)'
+                                 % (cid, ', '.join(str(i) for i in have)))
+            groups.append((int(cid), conformation_beads(store.chrom, store.copy, store.copy_ptr, store.copy_idx, cid,
+                                                        conformation_loci)))
     if out_dir is None:
         base = os.path.splitext(os.path.basename(hss_path))[0]
         out_dir = os.path.join(os.path.dirname(hss_path), 'QC_' + (label or base))
@@ -1209,6 +1381,27 @@ def report_population(hss_path, cfg=None, out_dir=None, steps=STEPS, label='', s
         feat = body_features(xyz, nbody, centre, assoc_cutoff, tsa_decay, **kw)
         np.savetxt(path('seeded_bodies/profiles%s.txt' % tag),
                    body_profiles(feat, nbody, store.copy_ptr, store.copy_idx))
+    if 'conformations' in steps:
+        rows, hists = [], []
+        for cid, beads in groups:
+            res = conformation_rmsd(xyz, beads, edges32, want_matrix=bool(save_rmsd), **kw)
+            sm = conformation_summary(res, xyz.shape[1])
+            rows.append((cid, beads.shape[1], beads.shape[0], len(res['g']), sm['mean'], sm['mean_rg'],
+                         sm['variability'], sm['medoid'][0], sm['medoid'][1], sm['medoid_mean_rmsd'],
+                         sm['same_mean'], sm['different_mean'], sm['ratio']))
+            hists.append(res['hist'])
+            np.savetxt(path('conformations/%d_mean_rmsd%s.txt' % (cid, tag)), sm['mean_rmsd'])
+            if save_rmsd:
+                np.save(path('conformations/%d_rmsd%s.npy' % (cid, tag)), res['rmsd'])
+        with open(path('conformations/summary%s.txt' % tag), 'w') as f:
+            f.write('# id nlocus ncopy M mean_rmsd mean_rg variability medoid_structure medoid_copy '
+                    'medoid_mean_rmsd same_structure_mean different_structure_mean ratio\n')
+            for r in rows:
+                f.write('%d %d %d %d %.17g %.17g %.17g %d %d %.17g %.17g %.17g %.17g\n' % r)
+        with open(path('conformations/histogram%s.txt' % tag), 'w') as f:
+            f.write('# lower upper %s\n' % ' '.join(str(cid) for cid, _ in groups))
+            for b in range(len(edges32) - 1):
+                f.write('%.9g %.9g %s\n' % (edges32[b], edges32[b + 1], ' '.join(str(int(h[b])) for h in hists)))
     if 'hic' in steps:
         from . import hss
         hcfg = params['hic']
@@ -1264,16 +1457,35 @@ def main(argv=None):
                     help='A bead this close to a body centre is associated with it (default: %(default)s)')
     ap.add_argument('--tsa-decay', type=float, default=DEFAULT_TSA_DECAY,
                     help='Decay of the predicted TSA-seq signal per length unit (default: %(default)s)')
+    ap.add_argument('--conformation-chroms', help='Comma separated chromosome ids (as in the index) of the '
+                                                  'conformations step (default: all)')
+    ap.add_argument('--conformation-loci', help='Text file with one 0/1 flag per haploid locus: the loci the '
+                                                'conformations step compares (default: all)')
+    ap.add_argument('--save-rmsd', action='store_true',
+                    help='Also write the full RMSD matrix of every chromosome of the conformations step')
+    ap.add_argument('--rmsd-max', type=float, default=DEFAULT_RMSD_MAX,
+                    help='Upper end of the RMSD histogram (default: %(default)s)')
+    ap.add_argument('--rmsd-bins', type=int, default=DEFAULT_RMSD_BINS,
+                    help='Bins of the RMSD histogram (default: %(default)s)')
     a = ap.parse_args(argv)
     if not os.path.isfile(a.hss):
         ap.error('Cannot find file %s' % a.hss)
+    chroms = None
+    if a.conformation_chroms is not None:
+        try:
+            chroms = [int(v) for v in a.conformation_chroms.split(',')]
+        except ValueError:
+            raise ValueError('--conformation-chroms takes comma separated integer ids, got %r'
+                             % a.conformation_chroms)
     written = report_population(a.hss, cfg=a.config, out_dir=a.out_dir, steps=a.steps, label=a.label,
                                 semiaxes=a.semiaxes, hic=a.hic, hic_sigma=a.hic_sigma,
                                 hic_inter_sigma=a.hic_inter_sigma, hic_intra_sigma=a.hic_intra_sigma,
                                 hic_contact_range=a.hic_contact_range, neighbour_cutoff=a.neighbour_cutoff,
                                 min_sep=a.min_sep, compaction_halfwidth=a.compaction_halfwidth, classes=a.classes,
                                 seeds=a.seeds, link_cutoff=a.link_cutoff, min_body_size=a.min_body_size,
-                                assoc_cutoff=a.assoc_cutoff, tsa_decay=a.tsa_decay)
+                                assoc_cutoff=a.assoc_cutoff, tsa_decay=a.tsa_decay, conformation_chroms=chroms,
+                                conformation_loci=a.conformation_loci, save_rmsd=a.save_rmsd,
+                                rmsd_edges=rmsd_edges_of(a.rmsd_max, a.rmsd_bins))
     for rel in sorted(written):
         print(written[rel])
     return 0

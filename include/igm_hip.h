@@ -880,6 +880,68 @@ int igm_report_body_features(igm_ctx* ctx, uint32_t flags,
                              double* nearest, double* dist_sum, double* dist_sqsum, int64_t* assoc,
                              double* tsa_sum);
 
+/* Pairwise conformation RMSD of chromosome copies: how different the structures of a
+ * population are from each other.  One call takes one group -- the ncopy copies of one
+ * chromosome, or of any subset of its loci -- over all nstruct structures and compares
+ * every two of its M = ncopy * nstruct conformations by their minimal RMSD after optimal
+ * rigid superposition (proper rotations only: a mirror image is not a match).  The
+ * definitions are this project's: the reference has no such report.  xyz (nbead, nstruct,
+ * 3) f32 as everywhere in the report; the models' length unit applies throughout.
+ *
+ *   bead (ncopy, nlocus) int32: the bead of locus i under copy k, any index table into
+ *        [0, nbead) (host pointer).  Conformation a = k * nstruct + s.
+ *
+ * Definitions, all float64: the centre c_a is the sum of the nlocus beads of a, widened and
+ * added in ascending locus order (in at most 16 contiguous runs whose sums are added in
+ * order), divided once by nlocus; p_i = f64(x_i) - c_a; g[a] = sum |p_i|^2 in the same
+ * order.  For a != b, m = sum_i p_i^a (x) p_i^b in ascending locus order, lambda the largest
+ * eigenvalue of Horn's key matrix of m (the tracing A-steps' solver: cyclic Jacobi, which
+ * takes collinear and coincident point sets), and
+ *     rmsd(a, b) = sqrt(max(0, (g_a + g_b - 2 lambda) / nlocus)),
+ * rounded once to float32.  Each unordered pair is computed once and mirrored: rmsd[a][b]
+ * and rmsd[b][a] are the same bits, and rmsd[a][a] = 0 exactly.  Error: within
+ * 1e-6 rmsd + sqrt(1e-12 (g_a + g_b) / nlocus) of exact arithmetic while nlocus <= 9000 (the
+ * float32 rounding plus the float64 cancellation in g_a + g_b - 2 lambda; identical
+ * conformations come out at that floor, not at 0).
+ *
+ * A conformation with a non-finite coordinate among its beads has g = NaN; its whole row
+ * and column of rmsd, the diagonal included, are NaN, and it is left out of row_sum, row_n,
+ * hist and everyone else's sums.
+ *
+ * Outputs; each may be NULL, not all.  Every reduction is available without the matrix
+ * (M^2 * 4 bytes) and has identical bytes whether or not rmsd is asked for; a rerun is
+ * bitwise equal in every output (fixed summation orders, no float atomics).
+ *   rmsd    (M, M) f32; follows `flags` (IGM_DEVICE_PTRS) like xyz.  Every other output is
+ *           a host pointer in every mode.
+ *   g       (M) f64
+ *   row_sum (M) f64: the sum over b != a of the finite rmsd(a, b), the float32 values
+ *           widened to float64 and added in ascending b (in runs of 64 conformations whose
+ *           sums are added in order)
+ *   row_n   (M) int32: the number of terms of row_sum
+ *   same    (nstruct, ncopy, ncopy) f32: same[s][k][k'] = rmsd((k, s), (k', s)), the copies
+ *           of one cell against each other, the matrix entries themselves (diagonal 0, or
+ *           NaN for a conformation with a non-finite coordinate)
+ *   hist    (nedge - 1) int64: counts of the finite rmsd(a, b) over a < b with
+ *           np.histogram's semantics on the float32 value: bins [e_i, e_i+1), the last one
+ *           closed; values outside the edges are not counted.  edges (nedge) f32, finite
+ *           and strictly increasing, nedge >= 2 (host pointer; NULL / 0 without hist, and
+ *           not read then).
+ *
+ * IGM_E_INVALID: a NULL xyz or bead; nbead, nstruct, ncopy or nlocus < 1; a bead index
+ * outside [0, nbead); hist with NULL edges, nedge < 2 or edges that are not finite and
+ * strictly increasing; every output NULL.  IGM_E_UNSUPPORTED: M > 2^20 (the tile grid and
+ * every index derived from M stay far inside their types), more than 4096 histogram bins
+ * (a workgroup counts them in LDS).  The context takes scratch of 24 * nlocus * M' bytes
+ * (the centred coordinates, M' = M rounded up to 64) and 12 * M' * M' / 64 (partial row
+ * sums); IGM_E_NOMEM when it cannot.  After any refusal no output is written and the
+ * context stays usable.  Timing: igm_last_kernel_ms "report_conformations". */
+int igm_report_conformations(igm_ctx* ctx, uint32_t flags,
+                             const float* xyz, int32_t nbead, int32_t nstruct,
+                             const int32_t* bead, int32_t ncopy, int32_t nlocus,
+                             const float* edges, int32_t nedge,
+                             float* rmsd, double* g, double* row_sum, int32_t* row_n,
+                             float* same, int64_t* hist);
+
 #ifdef __cplusplus
 }
 #endif
